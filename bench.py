@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: frames/s on paris-30k-like scenes, 1600x1600, MSAA16 (BASELINE config C3).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: it builds the scene, warms up, times exactly K steps and
+prints the line (value, ms_per_step, the workload and its bump counters).  --dump-outputs DIR writes the frame(s) of
+the last timed step (dump_outputs).  Everything below that goes beyond the headline -- roofline, one frame at a time,
+the fixed 200 steps, PCIe-inclusive rates, the exchange alone, r1mix, other_configs, cpu_baseline -- runs with --full.
 
 A "step" is one full pass of the pipeline (pathtag scan ... fine) over one resident packed scene, producing
 one RGBA8 frame in device memory.  With N > 1 every rank renders its own independent scene (seeds
@@ -270,8 +275,9 @@ def run_workload(wl, args, rank, local_rank, world, timed_headline):
     pipe = FramePipeline(nif, render=render, wait_frame=engine.sync_frame, exchange=exchange if distributed else local_done,
                          wait_exchange=lambda ev: ev.synchronize())
 
-    # warm-up, with every stage under HIP events to find the dominant kernel
-    engine.set_profiling(vello_amd.renderer.STAGES)
+    # warm-up (--full: with every stage under HIP events to find the dominant kernel)
+    if args.full:
+        engine.set_profiling(vello_amd.renderer.STAGES)
     for _ in range(max(args.warmup, 1)):
         pipe.step()
     pipe.flush()
@@ -279,23 +285,27 @@ def run_workload(wl, args, rank, local_rank, world, timed_headline):
     rc = engine.sync()
     if rc != 0:
         raise SystemExit(f"frame failed: {rc} {engine.bump()}")
-    engine.stage_ms()
-    engine.kernel_ms()  # (both read-and-reset: what follows is measured one frame at a time)
     bump = engine.bump()
     slice_items, cov_words = engine.fine_slice_stats()  # fine's long tiles cut into slices (engine.h FINE_SLICE_FILLS)
-    # the dominant kernel = the stage with the longest launch when frames run one at a time (with frames in flight a
-    # stage's events also span the other frames' kernels that share the CUs with it)
-    for _ in range(10):
-        engine.render_resident(WIDTH, HEIGHT, BASE_COLOR, aa, out=frame)
-        engine.sync_frame(0)
-    engine.sync()
-    iso_ms = engine.stage_ms()
-    # ... kernel by kernel: flatten and coarse are stages of several kernels (vello_hip_get_kernel_ms times them apart)
-    iso_k = engine.kernel_ms()
-    dominant_kernel, dominant, _, _ = dominant_of(engine, iso_ms, iso_k)  # (its stage: what the timed region's events go around)
+    fine_slices = {"slice_work_items": slice_items, "coverage_scratch_bytes": cov_words * 4,
+                   "rule": "MSAA: a tile of >= 96 FILLs (one frame in flight; >= 192 with frames in flight: the timed region slices nothing on d2) is cut into slices of 32 fills (coverage by one wave per slice, composited by the last to finish)"}
+    if args.full:
+        engine.stage_ms()
+        engine.kernel_ms()  # (both read-and-reset: what follows is measured one frame at a time)
+        # the dominant kernel = the stage with the longest launch when frames run one at a time (with frames in flight a
+        # stage's events also span the other frames' kernels that share the CUs with it)
+        for _ in range(10):
+            engine.render_resident(WIDTH, HEIGHT, BASE_COLOR, aa, out=frame)
+            engine.sync_frame(0)
+        engine.sync()
+        iso_ms = engine.stage_ms()
+        # ... kernel by kernel: flatten and coarse are stages of several kernels (vello_hip_get_kernel_ms times them apart)
+        iso_k = engine.kernel_ms()
+        dominant_kernel, dominant, _, _ = dominant_of(engine, iso_ms, iso_k)  # (its stage: what the timed region's events go around)
+        # timed region: events only around the dominant kernel (+ one completion event per frame)
+        engine.set_profiling([dominant])
 
-    # timed region: exactly K steps, events only around the dominant kernel (+ one completion event per frame)
-    engine.set_profiling([dominant])
+    # timed region: exactly K steps
     step_done.clear()
     if distributed:
         dist.barrier()
@@ -311,9 +321,10 @@ def run_workload(wl, args, rank, local_rank, world, timed_headline):
     elapsed = time.perf_counter() - t0
     if rc != 0:
         raise SystemExit(f"frame failed in the timed region: {rc} {engine.bump()}")
-    dom_ms, dom_n = engine.stage_ms()[dominant]
-    if dominant in engine.KERNELS:  # (the kernel's own share of its stage)
-        dom_ms, dom_n = engine.kernel_ms()[dominant_kernel]
+    # what the last timed step computed, copied to the host before anything else renders into the ring
+    outputs = None
+    if timed_headline and args.dump_outputs and rank == 0:
+        outputs = [f.cpu().numpy() for f in (gathered if distributed else [ring[(steps - 1) % nif]])]
     # completion-to-completion intervals of consecutive frames (each step waits for the oldest frame in flight)
     intervals = [(b - a) * 1e3 for a, b in zip(step_done[:-1], step_done[1:])]
     if distributed:
@@ -321,6 +332,17 @@ def run_workload(wl, args, rank, local_rank, world, timed_headline):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     own_fps = steps / elapsed
+    res = {
+        "engine": engine, "frame": frame, "steps": steps, "elapsed": elapsed, "own_fps": own_fps, "bump": bump, "outputs": outputs,
+        "fine_slices": fine_slices, "describe": wl.describe(engine),
+        "frame_ms": {"median": pct(intervals, 0.5), "p10": pct(intervals, 0.1), "p90": pct(intervals, 0.9), "mean": (sum(intervals) / len(intervals)) if intervals else None,
+                     "n": len(intervals)},
+    }
+    if not args.full:
+        return res
+    dom_ms, dom_n = engine.stage_ms()[dominant]
+    if dominant in engine.KERNELS:  # (the kernel's own share of its stage)
+        dom_ms, dom_n = engine.kernel_ms()[dominant_kernel]
 
     # the same pass once more over a FIXED 200 steps (">= 200 frames"): the driver's --steps is its own
     fps_200 = None
@@ -445,14 +467,9 @@ def run_workload(wl, args, rank, local_rank, world, timed_headline):
     # are the stage's bytes over the stage's time (all its kernels), not over the one kernel's
     frac_ms = stage_iso_ms if dominant in engine.KERNELS else iso_ms
     tile_area_bytes = 36 * bump["tile"]
-    res = {
-        "engine": engine, "frame": frame, "steps": steps, "elapsed": elapsed, "own_fps": own_fps, "bump": bump, "dominant": dominant, "dominant_kernel": dominant_kernel,
-        "fine_slices": {"slice_work_items": slice_items, "coverage_scratch_bytes": cov_words * 4,
-                        "rule": "MSAA: a tile of >= 96 FILLs (one frame in flight; >= 192 with frames in flight: the timed region slices nothing on d2) is cut into slices of 32 fills (coverage by one wave per slice, composited by the last to finish)"},
+    res.update({
+        "dominant": dominant, "dominant_kernel": dominant_kernel,
         "exchange_ms": exchange_ms, "pcie_fps": pcie_fps, "pcie_pipelined_fps": pcie_pipelined_fps,
-        "describe": wl.describe(engine),
-        "frame_ms": {"median": pct(intervals, 0.5), "p10": pct(intervals, 0.1), "p90": pct(intervals, 0.9), "mean": (sum(intervals) / len(intervals)) if intervals else None,
-                     "n": len(intervals)},
         "fps_200": fps_200,
         "frame_ms_200": {"median": pct(intervals_200, 0.5), "p10": pct(intervals_200, 0.1), "p90": pct(intervals_200, 0.9),
                          "mean": (sum(intervals_200) / len(intervals_200)) if intervals_200 else None, "n": len(intervals_200)},
@@ -495,8 +512,24 @@ def run_workload(wl, args, rank, local_rank, world, timed_headline):
             "kernel_ms_one_frame_in_flight": {k: round(v[0] / max(v[1], 1), 5) for k, v in lat_k.items()},
             "stage_algorithmic_bytes": {k: int(v) for k, v in sb.items()},
         },
-    }
+    })
     return res
+
+
+DUMP_SAMPLE = 1 << 20  # values per gathered frame in frames.npy (N > 1): 4 MB each, 32 MB at 8 GPUs
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: the RGBA8 frame(s) of the last timed step as float32 .npy files.  N = 1: frame.npy, the whole
+    (H, W, 4) frame (41 MB).  N > 1: frames.npy, (N, DUMP_SAMPLE) -- the same fixed, seeded sample of byte positions
+    (sorted, flat index into (H, W, 4)) of every rank's frame as rank 0 gathered it."""
+    os.makedirs(out_dir, exist_ok=True)
+    if len(frames) == 1:
+        np.save(os.path.join(out_dir, "frame.npy"), frames[0].astype(np.float32))
+        return
+    n = frames[0].size
+    idx = np.sort(np.random.default_rng(SEED0).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    np.save(os.path.join(out_dir, "frames.npy"), np.stack([f.reshape(-1)[idx] for f in frames]).astype(np.float32))
 
 
 def cpu_baseline(wl, frame):
@@ -552,12 +585,19 @@ def main():
                     help="frames the engine keeps in flight (wgpu queues recordings the same way); 1 = serial frames")
     ap.add_argument("--workload", choices=["both", "d2", "r1mix"], default="both",
                     help="d2 = SURVEY 8d d2's C3 scene (the workload of `value`); r1mix = round 1's mix; both = d2 + r1mix beside it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip config.other_configs (BASELINE's C2 / C4, ~1 s each)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, one frame at a time, 200 steps, PCIe, exchange alone, "
+                         "the r1mix workload, BASELINE's other configurations and the CPU baseline (without it: set-up, warm-up, timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame(s) of the last timed step to DIR/<name>.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip config.other_configs (BASELINE's C2 / C4, ~1 s each)")
     ap.add_argument("--timed-only", action="store_true",
-                    help="skip the serial / PCIe / CPU passes (for rocprofv3 runs: every launch it sees is then a "
-                         "warm-up or timed-region launch)")
+                    help="with --full: skip the serial / PCIe / CPU passes (for rocprofv3 runs: every launch it sees is then a "
+                         "warm-up, dominant-kernel or timed-region launch)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -576,10 +616,12 @@ def main():
 
     head_key = "r1mix" if args.workload == "r1mix" else "d2"
     head_wl = Workload(head_key, rank)
-    peak_measured = measure_copy_peak(local_rank) if rank == 0 else None
+    peak_measured = measure_copy_peak(local_rank) if (args.full and rank == 0) else None
     head = run_workload(head_wl, args, rank, local_rank, world, timed_headline=True)
+    if head["outputs"] is not None:
+        dump_outputs(args.dump_outputs, head["outputs"])
     second = None
-    if args.workload == "both" and not distributed and not args.timed_only:
+    if args.full and args.workload == "both" and not distributed and not args.timed_only:
         head["engine"] = None  # free the first context's pools before the second one allocates
         frame_head = head["frame"]
         second_wl = Workload("r1mix", rank)
@@ -604,8 +646,46 @@ def main():
     steps, elapsed = head["steps"], head["elapsed"]
     ms_per_step = elapsed / steps * 1e3
     value = world * steps / elapsed
-    dominant = head["dominant"]
+    result = {
+        "metric": "frames/sec paris-30k 1600x1600 MSAA16; scenes/sec at 1/2/4/8 GPU",
+        "value": round(value, 2),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32+u32",
+        "data": "synthetic",
+        "config": {
+            "workload": head["describe"],
+            "baseline_config": "configs[2]",
+            "commit": git_head(),
+            "fine_kernel": "k_fine",
+            "fine_slices": head["fine_slices"],
+            "parallelism": f"scenes{world}" if distributed else "single",
+            "exchange": "RCCL gather of RGBA8 frames to rank 0 each step" if distributed else "none",
+            "per_rank_frames_per_s": per_rank,
+            "bump": head["bump"],
+            "frames_in_flight": max(1, min(args.in_flight, 8)),
+            "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+            "frame_completion_interval_ms_pipelined": head["frame_ms"],
+            "frame_completion_interval_how": "host clock between consecutive frames' completions with --in-flight frames queued; completions come in bursts "
+                                             "(the frames in flight finish close together), so the MEDIAN interval is well below ms_per_step -- the mean is ms_per_step",
+        },
+    }
+    if args.full:
+        add_full_measurements(result, args, head, second, head_key, head_wl, frame_head, peak_measured, world, local_rank)
+    print(json.dumps(result))
+    if distributed:
+        dist.destroy_process_group()
 
+
+def add_full_measurements(result, args, head, second, head_key, head_wl, frame_head, peak_measured, world, local_rank):
+    """--full: the roofline of the dominant kernel, the one-frame-at-a-time, 200-step, PCIe-inclusive and exchange-alone
+    figures, the secondary workload, BASELINE's other configurations and the CPU baseline, added to the result line."""
     # HBM traffic of the dominant kernel from the PMC passes (collected separately, as the pool requires, by
     # scripts/gpu_calib.sh; corrected with the factors calibrated in the same session; stamped with its commit)
     traffic = traffic_commit = traffic_sources = None
@@ -636,47 +716,19 @@ def main():
                               f"collected at commit {traffic_commit}, kernel sources {traffic_sources}; this run's kernel sources {sources_now}: "
                               + ("STALE -- the kernels have changed since the PMC passes)" if stale else "the same kernels)"))
     serial_med = head["serial_ms"]["median"]
-    result = {
-        "metric": "frames/sec paris-30k 1600x1600 MSAA16; scenes/sec at 1/2/4/8 GPU",
-        "value": round(value, 2),
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32+u32",
-        "data": "synthetic",
-        "config": {
-            "workload": head["describe"],
-            "baseline_config": "configs[2]",
-            "commit": git_head(),
-            "fine_kernel": "k_fine",
-            "fine_slices": head["fine_slices"],
-            "parallelism": f"scenes{world}" if distributed else "single",
-            "exchange": "RCCL gather of RGBA8 frames to rank 0 each step" if distributed else "none",
-            "exchange_alone_ms": None if head["exchange_ms"] is None else round(head["exchange_ms"], 4),
-            "per_rank_frames_per_s": per_rank,
-            "bump": head["bump"],
-            "frames_in_flight": max(1, min(args.in_flight, 8)),
-            "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-            "frame_completion_interval_ms_pipelined": head["frame_ms"],
-            "frame_completion_interval_how": "host clock between consecutive frames' completions with --in-flight frames queued; completions come in bursts "
-                                             "(the frames in flight finish close together), so the MEDIAN interval is well below ms_per_step -- the mean is ms_per_step",
-            "value_200_steps": None if head["fps_200"] is None else round(head["fps_200"], 2),
-            "frame_completion_interval_ms_200_steps": head["frame_ms_200"],
-            "frame_ms_one_at_a_time": head["serial_ms"],
-            "value_one_frame_at_a_time": round(1e3 / serial_med, 2) if serial_med else None,
-            "one_frame_at_a_time_how": "vello_hip_set_frames_in_flight(1), then render + wait per frame on the host clock, median of 200 frames (SURVEY 8d d1 / b5: "
-                                       "one frame in flight per renderer); NOTE a different kernel configuration than `value`'s: with one frame in flight flatten "
-                                       "runs k_flatten_main / k_flatten_tail instead of k_flatten_strokes / k_flatten_heavy",
-            "pcie_inclusive_frames_per_s": None if head["pcie_fps"] is None else round(head["pcie_fps"], 2),
-            "pcie_inclusive_pipelined_frames_per_s": None if head["pcie_pipelined_fps"] is None else round(head["pcie_pipelined_fps"], 2),
-        },
-        "roofline": roof,
-    }
+    result["config"].update({
+        "exchange_alone_ms": None if head["exchange_ms"] is None else round(head["exchange_ms"], 4),
+        "value_200_steps": None if head["fps_200"] is None else round(head["fps_200"], 2),
+        "frame_completion_interval_ms_200_steps": head["frame_ms_200"],
+        "frame_ms_one_at_a_time": head["serial_ms"],
+        "value_one_frame_at_a_time": round(1e3 / serial_med, 2) if serial_med else None,
+        "one_frame_at_a_time_how": "vello_hip_set_frames_in_flight(1), then render + wait per frame on the host clock, median of 200 frames (SURVEY 8d d1 / b5: "
+                                   "one frame in flight per renderer); NOTE a different kernel configuration than `value`'s: with one frame in flight flatten "
+                                   "runs k_flatten_main / k_flatten_tail instead of k_flatten_strokes / k_flatten_heavy",
+        "pcie_inclusive_frames_per_s": None if head["pcie_fps"] is None else round(head["pcie_fps"], 2),
+        "pcie_inclusive_pipelined_frames_per_s": None if head["pcie_pipelined_fps"] is None else round(head["pcie_pipelined_fps"], 2),
+    })
+    result["roofline"] = roof
     if second is not None:
         smed = second["serial_ms"]["median"]
         result["config"]["secondary"] = {
@@ -701,9 +753,6 @@ def main():
         result["config"]["other_configs"] = others
     if world == 1 and not args.no_cpu_baseline and not args.timed_only:
         result["cpu_baseline"] = cpu_baseline(head_wl, frame_head)
-    print(json.dumps(result))
-    if distributed:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -9,5 +9,5 @@ which = sys.argv[1]
 import vello_amd._lib as L
 if which != "A":
     L._use_library(os.path.join(ROOT, "ab_tmp", f"libvello_hip_{which}.so"))
-sys.argv = ["bench.py"] + (sys.argv[2:] if len(sys.argv) > 2 else ["--steps", "200", "--warmup", "10", "--no-cpu-baseline"])
+sys.argv = ["bench.py"] + (sys.argv[2:] if len(sys.argv) > 2 else ["--full", "--steps", "200", "--warmup", "10", "--no-cpu-baseline"])
 runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")

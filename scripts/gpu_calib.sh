@@ -13,5 +13,5 @@ run() { # name counter cmd...
 }
 run calib_fetch FETCH_SIZE scripts/calib/pmc_calib
 run calib_write WRITE_SIZE scripts/calib/pmc_calib
-run eng_fetch FETCH_SIZE python bench.py --steps 10 --warmup 2 --in-flight 1 --timed-only
-run eng_write WRITE_SIZE python bench.py --steps 10 --warmup 2 --in-flight 1 --timed-only
+run eng_fetch FETCH_SIZE python bench.py --full --steps 10 --warmup 2 --in-flight 1 --timed-only
+run eng_write WRITE_SIZE python bench.py --full --steps 10 --warmup 2 --in-flight 1 --timed-only

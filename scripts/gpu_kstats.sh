@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 for wl in ${WL:-d2}; do
   rm -rf /tmp/ks; mkdir -p /tmp/ks
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o ks -- python bench.py --workload $wl --steps 20 --warmup 3 --in-flight 1 --timed-only > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o ks -- python bench.py --full --workload $wl --steps 20 --warmup 3 --in-flight 1 --timed-only > /dev/null 2>&1
   f=$(find /tmp/ks -name "*kernel_stats.csv" | head -1)
   echo "== $wl"; python - "$f" <<'PY'
 import csv, sys

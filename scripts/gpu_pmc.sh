@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/pmc
-CMD="python bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+CMD="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"
 run() { # name counters...
   name=$1; shift
   timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d gpurun_out/pmc/$name -o p -- $CMD > gpurun_out/pmc/$name.log 2>&1

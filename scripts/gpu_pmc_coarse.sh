@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/pmc
 WL=${WL:-d2}
-CMD="python bench.py --workload $WL --steps 6 --warmup 2 --in-flight 1 --timed-only"
+CMD="python bench.py --full --workload $WL --steps 6 --warmup 2 --in-flight 1 --timed-only"
 run() { # name counters...
   name=$1; shift
   timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d gpurun_out/pmc/$name -o p -- $CMD > gpurun_out/pmc/$name.log 2>&1

@@ -23,15 +23,15 @@ pmc() { # name counters -- cmd...
   rm -rf $OUT/tmp_$name
 }
 for wl in d2 r1mix; do
-  stats serial_$wl python bench.py --workload $wl --steps 50 --warmup 5 --in-flight 1 --timed-only
+  stats serial_$wl python bench.py --full --workload $wl --steps 50 --warmup 5 --in-flight 1 --timed-only
 done
-stats pipelined_d2 python bench.py --workload d2 --steps 100 --warmup 10 --timed-only
-python bench.py --workload d2 --steps 100 --warmup 10 --timed-only 2>/dev/null | tail -1 > $OUT/${TAG}_bench_timed_only_d2.json
+stats pipelined_d2 python bench.py --full --workload d2 --steps 100 --warmup 10 --timed-only
+python bench.py --full --workload d2 --steps 100 --warmup 10 --timed-only 2>/dev/null | tail -1 > $OUT/${TAG}_bench_timed_only_d2.json
 if [ ! -x scripts/calib/pmc_calib ]; then /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 scripts/calib/pmc_calib.hip -o scripts/calib/pmc_calib; fi
 pmc calib_fetch FETCH_SIZE -- scripts/calib/pmc_calib
 pmc calib_write WRITE_SIZE -- scripts/calib/pmc_calib
 for wl in d2 r1mix; do
-  CMD="python bench.py --workload $wl --steps 8 --warmup 2 --in-flight 1 --timed-only"
+  CMD="python bench.py --full --workload $wl --steps 8 --warmup 2 --in-flight 1 --timed-only"
   pmc fetch_$wl FETCH_SIZE -- $CMD
   pmc write_$wl WRITE_SIZE -- $CMD
   pmc sq1_$wl SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU -- $CMD

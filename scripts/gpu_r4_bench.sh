@@ -1,13 +1,14 @@
 #!/bin/bash
-# the bench line as the driver runs it (and with the defaults), saved under gpurun_out/r4bench
+# the bench line as the driver runs it (and with the defaults, --full), saved under $OUT/r4bench
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out/r4bench
-t0=$(date +%s.%N); python bench.py --steps 20 --warmup 5 > gpurun_out/r4bench/bench_k20.json 2> gpurun_out/r4bench/bench_k20.err; echo "bench.py wall: $(echo "$(date +%s.%N) - $t0" | bc) s"
-tail -3 gpurun_out/r4bench/bench_k20.err
+export OUT=${OUT:?set OUT to the directory for the results}
+mkdir -p "$OUT/r4bench"
+t0=$(date +%s.%N); python bench.py --full --steps 20 --warmup 5 > "$OUT/r4bench/bench_k20.json" 2> "$OUT/r4bench/bench_k20.err"; echo "bench.py wall: $(echo "$(date +%s.%N) - $t0" | bc) s"
+tail -3 "$OUT/r4bench/bench_k20.err"
 python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/r4bench/bench_k20.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ["OUT"], "r4bench", "bench_k20.json")).read().strip().splitlines()[-1])
 c = d["config"]; r = d["roofline"]
 print("value", d["value"], "ms/step", d["ms_per_step"], "one-frame", c["value_one_frame_at_a_time"], "200-step", c.get("value_200_steps"))
 print("roofline", r["kernel"], r["avg_launch_ms"], r["frac"], "peak_measured", r["peak_measured"], "frame_frac", r["frame_frac"], r.get("frame_frac_without_tile_area"))

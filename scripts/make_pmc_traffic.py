@@ -44,7 +44,7 @@ try:
 except OSError:
     pass
 doc = {
-    "note": "rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE collected in separate passes (kernel trace only) of `python bench.py --workload W "
+    "note": "rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE collected in separate passes (kernel trace only) of `python bench.py --full --workload W "
             "--steps 8 --warmup 2 --in-flight 1 --timed-only`; counters are in KiB, averaged per dispatch.  Corrections from the calibration "
             "kernels of the same session (scripts/calib/pmc_calib.hip, 512 MiB each): streamed 16 B/lane reads and writes.",
     "commit": commit,

@@ -1,5 +1,5 @@
 """What overlaps with what when frames are in flight: reads rocprofv3's kernel trace (start / end time stamps per dispatch) of
-`bench.py --timed-only --in-flight N` and prints, for the steady-state window, every kernel's mean duration under overlap, the
+`bench.py --full --timed-only --in-flight N` and prints, for the steady-state window, every kernel's mean duration under overlap, the
 chip's concurrency histogram (how long 0, 1, 2, ... kernels were running at once) and, per kernel, the mean number of OTHER
 kernels running beside it.    python scripts/pipeline_timeline.py <kernel_trace.csv>"""
 import csv

@@ -27,7 +27,7 @@ for aa in (AaConfig.Msaa8, AaConfig.Msaa16):
 PY
 for rep in 1 2; do
   for w in A B D E; do
-    timeout 90 python scripts/ab_bench.py $w --steps 80 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | line $w | tee -a $OUT/ab.txt
+    timeout 90 python scripts/ab_bench.py $w --full --steps 80 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | line $w | tee -a $OUT/ab.txt
   done
-  VELLO_FINE_PIPELINE=1 timeout 90 python scripts/ab_bench.py A --steps 80 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | line P | tee -a $OUT/ab.txt
+  VELLO_FINE_PIPELINE=1 timeout 90 python scripts/ab_bench.py A --full --steps 80 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | line P | tee -a $OUT/ab.txt
 done

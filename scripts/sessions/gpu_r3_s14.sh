@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/r3s14
 mkdir -p $OUT
 one() {
-  python scripts/ab_bench.py $2 --steps 80 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  python scripts/ab_bench.py $2 --full --steps 80 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['config']['secondary']
 f=lambda r: ' '.join('%s %.0f' % (k[:6], v*1e3) for k,v in r['stage_ms'].items() if v*1e3 >= 20)

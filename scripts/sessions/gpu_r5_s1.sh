@@ -11,7 +11,7 @@ timeout 300 python scripts/flatten_prof.py mmark tiger d2 2>&1 | grep -v amdgpu.
 timeout 200 python scripts/brush_prof.py stages 2>&1 | grep -v amdgpu.ids | tee $O/brush_stages.jsonl
 timeout 200 python scripts/brush_prof.py phases 2>&1 | grep -v amdgpu.ids | tee $O/brush_phases.txt
 timeout 400 python scripts/batch_estimate.py 2>&1 | grep -v amdgpu.ids | tee $O/batch_estimate.txt
-timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
+timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r5s1/bench.json").read().strip().splitlines()[-1])

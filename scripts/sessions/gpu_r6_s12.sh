@@ -10,5 +10,5 @@ cp .commit_stamp $OUT/commit.txt 2>/dev/null || true
  echo "== R5 library (ab_tmp/libvello_hip_R5.so), ring_last"; PROBE_LIBRARY=ab_tmp/libvello_hip_R5.so timeout 200 python scripts/bench_loop_probe.py ring_last 2>/dev/null | grep '"bare"'
 ) > $OUT/first_queue_fix.txt
 cat $OUT/first_queue_fix.txt
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_k20.json; head -c 300 $OUT/bench_k20.json; echo
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_k20_b.json; head -c 300 $OUT/bench_k20_b.json; echo
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_k20.json; head -c 300 $OUT/bench_k20.json; echo
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_k20_b.json; head -c 300 $OUT/bench_k20_b.json; echo

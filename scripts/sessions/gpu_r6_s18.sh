@@ -11,4 +11,4 @@ cp .commit_stamp $OUT/commit.txt 2>/dev/null || true
 timeout 120 python scripts/ab_process.py A d2 2>/dev/null > /dev/null
 for rep in 1 2 3; do for L in O A; do timeout 120 python scripts/ab_process.py $L d2 r1mix mmark tiger 2>/dev/null; done; done > $OUT/ab_slices_binning.txt
 cat $OUT/ab_slices_binning.txt
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_k20.json; head -c 300 $OUT/bench_k20.json; echo
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_k20.json; head -c 300 $OUT/bench_k20.json; echo

@@ -8,4 +8,4 @@ mkdir -p $OUT
 cp .commit_stamp $OUT/commit.txt 2>/dev/null || true
 timeout 300 python scripts/bench_loop_probe.py 2>/dev/null > $OUT/bench_loop_probe.txt
 cat $OUT/bench_loop_probe.txt
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | head -c 300; echo
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | head -c 300; echo

@@ -149,7 +149,7 @@ def test_frame_pipeline_exchanges_every_frame_once_in_order():
 # GPU-facing pieces replaced by recording fakes: torch.cuda.* no-ops, "nccl" -> gloo, an Engine that paints its rank
 # into the target.  What runs for real: argument/env handling, FramePipeline, gather_frames over gloo, the barrier /
 # all_reduce(MAX) timing protocol, the exchange-alone measurement and the JSON contract.
-def _bench_worker(rank, world, port, out_path):
+def _bench_worker(rank, world, port, out_path, extra_args=()):
     import io
     import json
     import runpy
@@ -209,7 +209,7 @@ def _bench_worker(rank, world, port, out_path):
 
         def render_resident(self, w, h, base, aa, out=None):
             calls["render"] += 1
-            out.fill_(rank + 1)
+            out.fill_(rank + 1 + 10 * (calls["render"] % 20))  # (rank and frame number: the dumped frame is the last step's)
 
         def render_frame(self, packed, layout, w, h, base, aa, out=None):
             out.fill_(rank + 1)
@@ -244,7 +244,7 @@ def _bench_worker(rank, world, port, out_path):
     real_d2 = workloads.paris_like_scene_d2
     workloads.paris_like_scene_d2 = lambda seed: real_d2(seed, n_paths=60, size=1600.0)
 
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "7", "--warmup", "2"]
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "7", "--warmup", "2", *extra_args]
     buf = io.StringIO()
     real_stdout = sys.stdout
     sys.stdout = buf
@@ -262,7 +262,7 @@ def test_bench_two_rank_control_flow(built, tmp_path):
 
     world = 2
     out = str(tmp_path / "bench")
-    mp.spawn(_bench_worker, args=(world, _free_port(), out), nprocs=world, join=True)
+    mp.spawn(_bench_worker, args=(world, _free_port(), out, ("--full",)), nprocs=world, join=True)
     r0 = json.load(open(out + ".0"))
     r1 = json.load(open(out + ".1"))
     assert len(r0["lines"]) == 1 and r1["lines"] == [], "rank 0 prints exactly ONE JSON line, other ranks none"
@@ -277,3 +277,34 @@ def test_bench_two_rank_control_flow(built, tmp_path):
     assert "cpu_baseline" not in line or line["cpu_baseline"] is None or line["n_gpus"] == 1
     assert line["roofline"]["kernel"] == "k_fine"
     assert r0["calls"]["render"] >= 9 and r1["calls"]["render"] >= 9
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_plain_run_times_steps_and_dumps_outputs(built, tmp_path, world):
+    """Without --full: warm-up + exactly --steps renders per rank, nothing beside them, the lean line, and --dump-outputs
+    writes the last timed step's frame(s) (rank 0's gather at N > 1) as float32."""
+    import json
+
+    out = str(tmp_path / "bench")
+    dump = str(tmp_path / "outputs")
+    mp.spawn(_bench_worker, args=(world, _free_port(), out, ("--dump-outputs", dump)), nprocs=world, join=True)
+    ranks = [json.load(open(f"{out}.{r}")) for r in range(world)]
+    assert len(ranks[0]["lines"]) == 1 and all(r["lines"] == [] for r in ranks[1:])
+    line = json.loads(ranks[0]["lines"][0])
+    assert line["n_gpus"] == world and line["steps"] == 7 and line["warmup"] == 2
+    assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32+u32"
+    assert abs(line["value"] - world * 7 / (line["ms_per_step"] * 7e-3)) / line["value"] < 1e-2
+    assert "roofline" not in line and "cpu_baseline" not in line and "value_200_steps" not in line["config"]
+    assert all(r["calls"]["render"] == 2 + 7 for r in ranks)  # (warm-up + timed steps, no other frame)
+    last = 1 + 10 * (9 % 20)  # the fake engine's fill of its 9th render, plus the rank
+    if world == 1:
+        assert os.listdir(dump) == ["frame.npy"]
+        frame = np.load(os.path.join(dump, "frame.npy"))
+        assert frame.dtype == np.float32 and frame.shape == (1600, 1600, 4)
+        assert (frame == last).all()
+    else:
+        assert os.listdir(dump) == ["frames.npy"]
+        frames = np.load(os.path.join(dump, "frames.npy"))
+        assert frames.dtype == np.float32 and frames.shape == (world, 1 << 20)  # (bench.DUMP_SAMPLE)
+        for r in range(world):
+            assert (frames[r] == last + r).all()
