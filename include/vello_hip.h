@@ -20,6 +20,9 @@
  *   vello_hip_render_resident  the Dispatch/DispatchIndirect chain       vello/src/render.rs:250-502, :560-629
  *   vello_hip_resize_image_atlas  ImageProxy::new(atlas_width, atlas_height)  vello/src/render.rs:160-176
  *   vello_hip_write_image      Recording::write_image(image_atlas, x, y, ..) vello/src/render.rs:201-203
+ *   vello_hip_copy_images_device  the image_overrides branch of         vello/src/wgpu_engine.rs:486-504,
+ *                              Command::WriteImage (copy_texture_to_texture) vello/src/lib.rs:536-555
+ *                              for Renderer::override_image / register_texture
  *   vello_hip_sync             queue.submit + device.poll                vello/src/wgpu_engine.rs:757
  *   vello_hip_set_frames_in_flight  back-to-back queue.submit without waiting  vello/src/wgpu_engine.rs:757
  *   vello_hip_get_bump         the robust path's bump download           vello/src/lib.rs:730, :753-761
@@ -185,6 +188,25 @@ int vello_hip_render_frame(vello_hip_ctx *ctx, const uint8_t *scene, size_t scen
 int vello_hip_resize_image_atlas(vello_hip_ctx *ctx, uint32_t width, uint32_t height);
 int vello_hip_write_image(vello_hip_ctx *ctx, uint32_t x, uint32_t y, uint32_t width, uint32_t height, const uint8_t *rgba8,
                           size_t stride /* bytes per source row; 0 = width*4 */);
+
+/* One rectangle of a device-to-atlas copy: `src` is the device address (on the context's device) of the first of `height`
+ * rows of `width` RGBA8 words, `src_stride` bytes apart (0 = width * 4).  Source address and stride are multiples of 4. */
+typedef struct vello_hip_image_copy {
+    uint64_t src;
+    uint64_t src_stride;
+    uint32_t x, y, width, height;
+} vello_hip_image_copy;
+
+/* Image overrides (Renderer::override_image / register_texture): copies `n` rectangles of device memory into the atlas in ONE
+ * kernel launch (k_atlas_copy), texels verbatim (format and alpha type are applied while sampling, as for write_image).
+ * Ordered like vello_hip_write_image -- behind every frame enqueued before it, in front of every frame enqueued after it --
+ * and, when `src_stream` (a hipStream_t, nullable) is given, behind the work enqueued on it so far; `src_stream` then waits for
+ * the copy, so work the caller enqueues there afterwards may overwrite the sources.  Nothing waits on the host.
+ * VELLO_HIP_E_INVALID, with nothing enqueued, for a rectangle outside the atlas, a null or unaligned source of a rectangle
+ * that is not empty, copies == NULL with n > 0, or (GPU builds) a source that is not device memory of the context's device.
+ * n == 0 and empty rectangles do nothing.  The rectangles of one batch run concurrently: their destinations must not overlap
+ * (no rectangle is "later" than another), and a source must not lie in the atlas itself. */
+int vello_hip_copy_images_device(vello_hip_ctx *ctx, const vello_hip_image_copy *copies, uint32_t n, void *src_stream /* nullable hipStream_t */);
 
 /* Robust dynamic memory.  vello_hip_grow_pools re-sizes every pool whose counter in `demand`
  * (from vello_hip_get_bump / bump_out after VELLO_HIP_E_CAPACITY) exceeds it, with 25 % headroom, on all in-flight

@@ -59,6 +59,18 @@ pub struct vello_hip_capacities {
     pub ptcl: u32,
 }
 
+/// One rectangle of `vello_hip_copy_images_device`: `src` is a device address on the context's GPU.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vello_hip_image_copy {
+    pub src: u64,
+    pub src_stride: u64,
+    pub x: u32,
+    pub y: u32,
+    pub width: u32,
+    pub height: u32,
+}
+
 pub const VELLO_HIP_AA_AREA: u32 = 0;
 pub const VELLO_HIP_AA_MSAA8: u32 = 1;
 pub const VELLO_HIP_AA_MSAA16: u32 = 2;
@@ -90,6 +102,7 @@ unsafe extern "C" {
     pub fn vello_hip_render_frame(ctx: *mut vello_hip_ctx, scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, params: *const vello_hip_render_params, ramps: *const u32, n_ramps: u32, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_resize_image_atlas(ctx: *mut vello_hip_ctx, width: u32, height: u32) -> c_int;
     pub fn vello_hip_write_image(ctx: *mut vello_hip_ctx, x: u32, y: u32, width: u32, height: u32, rgba8: *const u8, stride: usize) -> c_int;
+    pub fn vello_hip_copy_images_device(ctx: *mut vello_hip_ctx, copies: *const vello_hip_image_copy, n: u32, src_stream: *mut c_void) -> c_int;
     pub fn vello_hip_get_capacities(ctx: *mut vello_hip_ctx, out: *mut vello_hip_capacities) -> c_int;
     pub fn vello_hip_grow_pools(ctx: *mut vello_hip_ctx, demand: *const vello_hip_bump, new_caps: *mut vello_hip_capacities) -> c_int;
     pub fn vello_hip_last_render_attempts(ctx: *mut vello_hip_ctx) -> u32;

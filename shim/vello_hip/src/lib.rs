@@ -10,7 +10,9 @@ pub mod ffi;
 
 use core::ffi::{c_int, c_void, CStr};
 use ffi::*;
+use std::collections::HashMap;
 use vello::{AaConfig, AaSupport, RenderParams, Scene};
+use vello::peniko::ImageData;
 use vello_encoding::{Layout, Resolver};
 
 #[derive(Debug)]
@@ -29,11 +31,22 @@ pub enum Error {
     Internal(String),
 }
 
+/// What `override_image` binds to an image in place of its pixels -- upstream a `wgpu::TexelCopyTextureInfoBase<Texture>`
+/// (vello/src/lib.rs:536-545), here a device address on the renderer's GPU: `src` points at the texel of the image's
+/// origin, rows of RGBA8 words `stride` bytes apart (0 = width * 4).  The caller keeps the memory alive while it is bound.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct DeviceTexture {
+    pub src: u64,
+    pub stride: u64,
+}
+
 pub struct HipRenderer {
     ctx: *mut vello_hip_ctx,
     resolver: Resolver,
     packed: Vec<u8>,
     atlas_size: (u32, u32),
+    /// `WgpuEngine::image_overrides` (vello/src/wgpu_engine.rs:486-504): blob id -> device source
+    overrides: HashMap<u64, DeviceTexture>,
 }
 // Renderer: Send, !Sync (vello/src/lib.rs:351-352): a context is single-threaded, different contexts are independent
 unsafe impl Send for HipRenderer {}
@@ -69,7 +82,23 @@ impl HipRenderer {
         }
         // the robust path upstream is a TODO (lib.rs:753-764); here a frame that overflows grows the pools and re-runs
         unsafe { vello_hip_set_auto_grow(ctx, 1) };
-        Ok(Self { ctx, resolver: Resolver::new(), packed: Vec::new(), atlas_size: (0, 0) })
+        Ok(Self { ctx, resolver: Resolver::new(), packed: Vec::new(), atlas_size: (0, 0), overrides: HashMap::new() })
+    }
+
+    /// `Renderer::override_image` (vello/src/lib.rs:536-545): whenever the resolver schedules `image` for upload, its texels
+    /// are copied from `texture` (device to atlas, batched with the frame's other overrides) instead of its blob; `None`
+    /// removes the override.  Marks the image dirty; returns the previous source.
+    pub fn override_image(&mut self, image: &ImageData, texture: Option<DeviceTexture>) -> Option<DeviceTexture> {
+        self.resolver.mark_image_dirty(image);
+        match texture {
+            Some(texture) => self.overrides.insert(image.data.id(), texture),
+            None => self.overrides.remove(&image.data.id()),
+        }
+    }
+
+    /// `Renderer::mark_override_image_dirty` (vello/src/lib.rs:547-555): the source's contents changed.
+    pub fn mark_override_image_dirty(&mut self, image: &ImageData) {
+        self.resolver.mark_image_dirty(image);
     }
 
     /// What a failed call left in the context.  A free function over the raw context pointer (not `&self`): it is called
@@ -93,44 +122,84 @@ impl HipRenderer {
         // identical to Render::render_encoding_coarse up to the uploads (vello/src/render.rs:135-232).
         // Borrows: `resolve` borrows `self.resolver` mutably for as long as `ramps` / `images` live, and `self.packed`
         // for the call only.  Everything below therefore touches `self` through DISJOINT fields (`self.ctx`, a `Copy`
-        // raw pointer read once up front; `self.atlas_size`; `self.packed`) and never through a `&self` / `&mut self`
-        // method, which would borrow all of `self` while the resolver is lent out (E0502).
+        // raw pointer read once up front; `self.atlas_size`; `self.packed`; `self.overrides`, lent out before the resolve) and
+        // never through a `&self` / `&mut self` method, which would borrow all of `self` while the resolver is lent out (E0502).
         let ctx = self.ctx;
+        // (a shared loan of the `overrides` field, disjoint from the resolver's)
+        let overrides = &self.overrides;
         let (layout, ramps, images) = self.resolver.resolve(scene.encoding(), &mut self.packed);
-        // vello/src/render.rs:160-203: the persistent image atlas follows the Resolver's image cache
-        if (images.width, images.height) != self.atlas_size {
-            let rc = unsafe { vello_hip_resize_image_atlas(ctx, images.width, images.height) };
-            if rc != VELLO_HIP_OK {
-                return Err(Self::error(ctx, rc, vello_hip_bump::default()));
-            }
-            self.atlas_size = (images.width, images.height);
-        }
-        // `images.images: &[(ImageData, u32, u32)]` (vello_encoding/src/image_cache.rs:24): iterate by reference
-        for (image, x, y) in images.images.iter() {
-            let bytes: &[u8] = image.data.data();
-            let rc = unsafe { vello_hip_write_image(ctx, *x, *y, image.width, image.height, bytes.as_ptr(), 0) };
-            if rc != VELLO_HIP_OK {
-                return Err(Self::error(ctx, rc, vello_hip_bump::default()));
-            }
-        }
-        let p = vello_hip_render_params {
-            width: params.width,
-            height: params.height,
-            base_color: params.base_color.premultiply().to_rgba8().to_u32(), // vello_encoding/src/config.rs:183
-            aa: match params.antialiasing_method {
-                AaConfig::Area => VELLO_HIP_AA_AREA,
-                AaConfig::Msaa8 => VELLO_HIP_AA_MSAA8,
-                AaConfig::Msaa16 => VELLO_HIP_AA_MSAA16,
-            },
-        };
-        let hl = to_hip_layout(&layout);
+        // `images.images: &[(ImageData, u32, u32)]` (vello_encoding/src/image_cache.rs:24): iterate by reference.  An image
+        // with neither an override nor pixels is refused before anything is enqueued (wgpu_engine.rs:505-514 panics); the
+        // frame's images are kept (cheap clones: a blob is an Arc) to be marked dirty again once the resolver's loans end.
+        let refused: Option<(u64, Vec<ImageData>)> = images
+            .images
+            .iter()
+            .find(|(image, _, _)| {
+                overrides.get(&image.data.id()).is_none() && image.data.data().is_empty() && image.width != 0 && image.height != 0
+            })
+            .map(|(image, _, _)| (image.data.id(), images.images.iter().map(|(im, _, _)| im.clone()).collect()));
+        let rc;
         let mut bump = vello_hip_bump::default();
-        // `Ramps { data: &[u32], width, height }` is `Copy` (ramp_cache.rs:16-21); an empty slice's pointer is dangling but
-        // non-null and is never read (n_ramps = 0)
-        let rc = unsafe {
-            vello_hip_render(ctx, self.packed.as_ptr(), self.packed.len(), &hl, &p, ramps.data.as_ptr(), ramps.height,
-                             target, stride, on_device as c_int, &mut bump)
-        };
+        if refused.is_some() {
+            rc = VELLO_HIP_E_INVALID;
+        } else {
+            // vello/src/render.rs:160-203: the persistent image atlas follows the Resolver's image cache
+            if (images.width, images.height) != self.atlas_size {
+                let rc = unsafe { vello_hip_resize_image_atlas(ctx, images.width, images.height) };
+                if rc != VELLO_HIP_OK {
+                    return Err(Self::error(ctx, rc, vello_hip_bump::default()));
+                }
+                self.atlas_size = (images.width, images.height);
+            }
+            // overrides: ONE device-to-atlas batch (wgpu_engine.rs:486-504 copies texture to texture per image); blobs: host writes
+            let mut copies: Vec<vello_hip_image_copy> = Vec::new();
+            for (image, x, y) in images.images.iter() {
+                if let Some(t) = overrides.get(&image.data.id()) {
+                    copies.push(vello_hip_image_copy { src: t.src, src_stride: t.stride, x: *x, y: *y, width: image.width, height: image.height });
+                    continue;
+                }
+                let bytes: &[u8] = image.data.data();
+                let rc = unsafe { vello_hip_write_image(ctx, *x, *y, image.width, image.height, bytes.as_ptr(), 0) };
+                if rc != VELLO_HIP_OK {
+                    return Err(Self::error(ctx, rc, vello_hip_bump::default()));
+                }
+            }
+            if !copies.is_empty() {
+                let rc = unsafe { vello_hip_copy_images_device(ctx, copies.as_ptr(), copies.len() as u32, core::ptr::null_mut()) };
+                if rc != VELLO_HIP_OK {
+                    return Err(Self::error(ctx, rc, vello_hip_bump::default()));
+                }
+            }
+            let p = vello_hip_render_params {
+                width: params.width,
+                height: params.height,
+                base_color: params.base_color.premultiply().to_rgba8().to_u32(), // vello_encoding/src/config.rs:183
+                aa: match params.antialiasing_method {
+                    AaConfig::Area => VELLO_HIP_AA_AREA,
+                    AaConfig::Msaa8 => VELLO_HIP_AA_MSAA8,
+                    AaConfig::Msaa16 => VELLO_HIP_AA_MSAA16,
+                },
+            };
+            let hl = to_hip_layout(&layout);
+            // `Ramps { data: &[u32], width, height }` is `Copy` (ramp_cache.rs:16-21); an empty slice's pointer is dangling but
+            // non-null and is never read (n_ramps = 0)
+            rc = unsafe {
+                vello_hip_render(ctx, self.packed.as_ptr(), self.packed.len(), &hl, &p, ramps.data.as_ptr(), ramps.height,
+                                 target, stride, on_device as c_int, &mut bump)
+            };
+        }
+        if let Some((id, again)) = refused {
+            // resolve() marked these images resident and clean: ask for them again, so that a source bound after this failure is
+            // copied by the next render (vello_amd/csrc/host/renderer.cpp does the same)
+            for image in &again {
+                self.resolver.mark_image_dirty(image);
+            }
+            return Err(Error::Invalid(format!(
+                "Tried to draw an invalid empty image (id {}). Maybe it was registered to a different renderer, or \
+                 unregistered before this render was submitted.",
+                id
+            )));
+        }
         if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(ctx, rc, bump)) }
     }
 

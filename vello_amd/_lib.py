@@ -43,6 +43,10 @@ class RenderParamsStruct(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("width", "height", "base_color", "aa")]
 
 
+class ImageCopyStruct(ctypes.Structure):  # vello_hip_image_copy
+    _fields_ = [("src", ctypes.c_uint64), ("src_stride", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in ("x", "y", "width", "height")]
+
+
 def load_library():
     """Loads the product library; raises (never falls back) when it is missing."""
     global _LIB
@@ -85,6 +89,7 @@ def load_library():
     sig("vello_hip_set_frames_in_flight", i32, [vp, u32])
     sig("vello_hip_resize_image_atlas", i32, [vp, u32, u32])
     sig("vello_hip_write_image", i32, [vp, u32, u32, u32, u32, vp, sz])
+    sig("vello_hip_copy_images_device", i32, [vp, c.POINTER(ImageCopyStruct), u32, vp])
     sig("vello_hip_get_capacities", i32, [vp, c.POINTER(Capacities)])
     sig("vello_hip_grow_pools", i32, [vp, c.POINTER(Bump), c.POINTER(Capacities)])
     sig("vello_hip_set_auto_grow", i32, [vp, i32])
@@ -147,6 +152,7 @@ def load_library():
     sig("vh_resolver_free", None, [vp])
     sig("vh_resolver_resolve", sz, [vp, vp, c.POINTER(vp), c.POINTER(u32), c.POINTER(vp), c.POINTER(u32)])
     sig("vh_resolver_upload", vp, [vp, u32, c.POINTER(u32)])
+    sig("vh_resolver_upload_id", c.c_uint64, [vp, u32])
     sig("vh_resolver_mark_image_dirty", None, [vp, c.c_uint64])
     sig("vh_resolver_image_cache_info", None, [vp, c.POINTER(u32)])
     sig("vh_scene_stream_bytes", sz, [vp, i32])
@@ -160,6 +166,9 @@ def load_library():
     sig("vh_renderer_new", vp, [i32, u32, c.POINTER(Capacities), c.c_char_p, sz])
     sig("vh_renderer_free", None, [vp])
     sig("vh_renderer_render_to_texture", i32, [vp, vp, vp, sz, i32, u32, u32, fp, u32])
+    sig("vh_renderer_render_to_texture_on", i32, [vp, vp, vp, sz, i32, u32, u32, fp, u32, vp])
+    sig("vh_renderer_override_image", i32, [vp, c.c_uint64, i32, c.c_uint64, c.c_uint64, c.POINTER(c.c_uint64)])
+    sig("vh_renderer_mark_override_image_dirty", None, [vp, c.c_uint64])
     sig("vh_renderer_error", c.c_char_p, [vp])
     sig("vh_renderer_engine", vp, [vp])
     sig("vh_renderer_last_bump", None, [vp, c.POINTER(Bump)])

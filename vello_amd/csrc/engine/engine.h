@@ -224,4 +224,18 @@ int enable_coarse_lds();  // hipError_t of the per-device dynamic-LDS opt-in
 void launch_path_tiling(const Frame &f, hipStream_t s);
 void launch_fine(const Frame &f, hipStream_t s);
 
+// Device-to-atlas copies (vello_hip_copy_images_device, engine.hip): one rectangle of raw RGBA8 words per entry.  `first` is
+// the exclusive prefix of width * height over the batch, so the batch is one concatenated texel space that k_atlas_copy
+// cuts into equal chunks whatever the rectangles' sizes.  Zero-sized rectangles are left out of the table by the host.
+struct AtlasCopyDesc {
+    uint64_t src;         // device address of the source's first texel
+    uint64_t src_stride;  // bytes between source rows (a multiple of 4)
+    uint64_t dst;         // atlas texel index of the destination's first texel: y * atlas_w + x
+    uint64_t first;       // texels of the entries before this one
+    uint32_t width, height;
+};
+static_assert(sizeof(AtlasCopyDesc) == 40, "AtlasCopyDesc");
+// `descs`: n entries in device memory, `total` = the last entry's first + its texels (> 0)
+void launch_atlas_copy(const AtlasCopyDesc *descs, uint32_t n, uint64_t total, uint32_t *atlas, uint32_t atlas_w, hipStream_t s);
+
 }  // namespace vk

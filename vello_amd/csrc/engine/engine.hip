@@ -7,12 +7,60 @@
 
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
 #include "engine.h"
 
 using namespace vk;
+
+namespace vk {
+
+// k_atlas_copy: the rectangles of one vello_hip_copy_images_device call as ONE concatenated texel space, cut into chunks of
+// `steps` x 256 texels, a chunk per workgroup.  Lane i of a wave takes texel base + i, so a wave reads and writes 64
+// consecutive dwords of a row (or the tail of one row and the head of the next); a thousand 16x16 sprites are 1 000
+// workgroups of full waves, not 16 000 rows of quarter waves, and a 4K frame is 2 000 workgroups.  A thread finds its
+// first texel's rectangle by binary search over the host's prefix and walks on from there by the 256-texel step.
+// Plain dword accesses: the atlas x is arbitrary, so a destination row is only 4-byte aligned.
+constexpr uint32_t ATLAS_COPY_MAX_STEPS = 16u, ATLAS_COPY_TARGET_WGS = 2048u;
+
+__global__ void __launch_bounds__(256) k_atlas_copy(const AtlasCopyDesc *__restrict__ descs, uint32_t n, uint64_t total, uint32_t steps,
+                                                    uint32_t *__restrict__ atlas, uint32_t atlas_w) {
+    uint64_t t = (uint64_t)blockIdx.x * steps * 256u + threadIdx.x;
+    if (t >= total) return;
+    uint32_t lo = 0u, hi = n - 1u;  // the last entry whose first <= t
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (descs[mid].first <= t) lo = mid;
+        else hi = mid - 1u;
+    }
+    uint32_t r = lo;
+    AtlasCopyDesc d = descs[r];
+    uint64_t local = t - d.first;
+    for (uint32_t k = 0; k < steps && t < total; k++, t += 256u, local += 256u) {
+        uint64_t size = (uint64_t)d.width * d.height;
+        while (local >= size) {  // (t < total: a later entry holds it; every entry of the table holds texels)
+            local -= size;
+            d = descs[++r];
+            size = (uint64_t)d.width * d.height;
+        }
+        const uint32_t li = (uint32_t)local;  // < width * height <= 65535^2
+        const uint32_t row = li / d.width, col = li - row * d.width;
+        const uint32_t v = *(const uint32_t *)(uintptr_t)(d.src + (uint64_t)row * d.src_stride + (uint64_t)col * 4u);
+        atlas[d.dst + (uint64_t)row * atlas_w + col] = v;
+    }
+}
+
+void launch_atlas_copy(const AtlasCopyDesc *descs, uint32_t n, uint64_t total, uint32_t *atlas, uint32_t atlas_w, hipStream_t s) {
+    // enough steps per workgroup that the grid stays near ATLAS_COPY_TARGET_WGS (8 per CU), at most ATLAS_COPY_MAX_STEPS
+    uint64_t steps = (total + 256u * ATLAS_COPY_TARGET_WGS - 1u) / (256u * ATLAS_COPY_TARGET_WGS);
+    steps = steps < 1u ? 1u : steps > ATLAS_COPY_MAX_STEPS ? ATLAS_COPY_MAX_STEPS : steps;
+    const uint64_t wgs = (total + steps * 256u - 1u) / (steps * 256u);
+    hipLaunchKernelGGL(k_atlas_copy, dim3((uint32_t)wgs), dim3(256), 0, s, descs, n, total, (uint32_t)steps, atlas, atlas_w);
+}
+
+}  // namespace vk
 
 namespace {
 
@@ -118,6 +166,7 @@ struct vello_hip_ctx {
     hipEvent_t stage_turn[VELLO_HIP_STAGE_COUNT] = {};
     uint64_t atlas_epoch = 0;  // uploads enqueued so far
     std::vector<Staging> staging;
+    DevBuf copy_descs;  // vello_hip_copy_images_device: the batch's AtlasCopyDesc table (written and read on the upload stream only)
     uint32_t debug_flags = 0;  // VELLO_HIP_DEBUG_*
     bool force_brushes = false;  // pre-warm: run fine's brush specialisation on a scene without brushes
     uint32_t last_render_attempts = 0;  // rounds the last vello_hip_render needed (robust mode)
@@ -856,7 +905,7 @@ void vello_hip_destroy(vello_hip_ctx *c) {
     for (auto &l : c->lanes)
         for (DevBuf *b : {&l.own.scene, &l.own.ramps})
             if (b->ptr) (void)hipFree(b->ptr);
-    for (DevBuf *b : {&c->shared.scene, &c->shared.ramps, &c->config, &c->mask8, &c->mask16, &c->atlas})
+    for (DevBuf *b : {&c->shared.scene, &c->shared.ramps, &c->config, &c->mask8, &c->mask16, &c->atlas, &c->copy_descs})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -1047,6 +1096,100 @@ int vello_hip_write_image(vello_hip_ctx *c, uint32_t x, uint32_t y, uint32_t wid
     // ... and every frame enqueued from here on runs behind it (prepare_frame)
     HIP_TRY(c, hipEventRecord(c->atlas_ready, c->upload_stream));
     c->atlas_epoch += 1u;
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_copy_images_device(vello_hip_ctx *c, const vello_hip_image_copy *copies, uint32_t n, void *src_stream) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    if (n > 0u && !copies) {
+        c->last_error = "copy_images_device: copies is NULL";
+        return VELLO_HIP_E_INVALID;
+    }
+    // every rectangle is checked before anything is enqueued
+    uint64_t total = 0;
+    uint32_t m = 0;
+#ifndef VELLO_SIMT_EMU
+    std::map<uint64_t, uint64_t> checked;  // allocations found to be device memory of this device: base -> end
+#endif
+    for (uint32_t i = 0; i < n; i++) {
+        const vello_hip_image_copy &cp = copies[i];
+        if (cp.width == 0u || cp.height == 0u) continue;
+        const std::string which = "copy_images_device: rectangle " + std::to_string(i);
+        if ((uint64_t)cp.x + cp.width > c->atlas_w || (uint64_t)cp.y + cp.height > c->atlas_h) {
+            c->last_error = which + " outside the atlas";
+            return VELLO_HIP_E_INVALID;
+        }
+        const uint64_t stride = cp.src_stride ? cp.src_stride : (uint64_t)cp.width * 4u;
+        if (cp.src == 0u || ((cp.src | stride) & 3u) != 0u) {
+            c->last_error = which + (cp.src ? ": source address or row stride not a multiple of 4" : ": null source");
+            return VELLO_HIP_E_INVALID;
+        }
+#ifndef VELLO_SIMT_EMU
+        // every byte the rectangle reads lies in ONE allocation in device memory of this context's device (peer sources are not
+        // taken); one runtime query per allocation, not per rectangle: a thousand sprites carved from one tensor cost one
+        const uint64_t last = cp.src + (uint64_t)(cp.height - 1u) * stride + (uint64_t)cp.width * 4u - 1u;
+        auto known = checked.upper_bound(cp.src);
+        if (known == checked.begin() || (--known, last >= known->second)) {
+            hipDeviceptr_t base = nullptr;
+            size_t size = 0;
+            hipPointerAttribute_t attr{};
+            hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)(uintptr_t)cp.src);
+            if (e == hipSuccess) e = hipPointerGetAttributes(&attr, base);
+            (void)hipGetLastError();  // a host address is an error here: do not leave it for the caller's next launch check
+            const uint64_t b = (uint64_t)(uintptr_t)base;
+            if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != c->device || last >= b + size) {
+                c->last_error = which + (e == hipSuccess && last >= b + size ? ": source rows run past the end of their allocation"
+                                                                              : ": source is not device memory of device " + std::to_string(c->device));
+                return VELLO_HIP_E_INVALID;
+            }
+            checked[b] = b + size;
+        }
+#endif
+        total += (uint64_t)cp.width * cp.height;
+        m++;
+    }
+    if (m == 0u) return VELLO_HIP_OK;
+    if (total > ((uint64_t)1 << 40)) {  // (k_atlas_copy's grid is a 32-bit count of 4 096-texel chunks)
+        c->last_error = "copy_images_device: more than 2^40 texels in one batch";
+        return VELLO_HIP_E_INVALID;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int r = ensure_upload_stream(c);
+    if (r) return r;
+    const size_t table_bytes = (size_t)m * sizeof(AtlasCopyDesc);
+    Staging *st = nullptr;
+    if ((r = acquire_staging(c, table_bytes, st))) return r;
+    // (ensure() replaces a table too small with hipFree + hipMalloc; hipFree waits for the copies still reading the old one)
+    if ((r = ensure(c, c->copy_descs, table_bytes))) return r;
+    AtlasCopyDesc *table = (AtlasCopyDesc *)st->host;
+    uint64_t first = 0;
+    for (uint32_t i = 0, k = 0; i < n; i++) {
+        const vello_hip_image_copy &cp = copies[i];
+        if (cp.width == 0u || cp.height == 0u) continue;
+        table[k++] = AtlasCopyDesc{cp.src, cp.src_stride ? cp.src_stride : (uint64_t)cp.width * 4u, (uint64_t)cp.y * c->atlas_w + cp.x, first,
+                                   cp.width, cp.height};
+        first += (uint64_t)cp.width * cp.height;
+    }
+    // behind the frames already enqueued (they may sample the texels this copy replaces), as write_image ...
+    for (auto &l : c->lanes) {
+        if (!l.stream || !l.used) continue;
+        HIP_TRY(c, hipEventRecord(c->lane_mark, l.stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->upload_stream, c->lane_mark, 0));
+    }
+    // ... and behind the caller's work that produced the sources
+    if (src_stream) {
+        HIP_TRY(c, hipEventRecord(c->lane_mark, (hipStream_t)src_stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->upload_stream, c->lane_mark, 0));
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->copy_descs.ptr, st->host, table_bytes, hipMemcpyHostToDevice, c->upload_stream));
+    HIP_TRY(c, hipEventRecord(st->done, c->upload_stream));
+    st->busy = true;
+    launch_atlas_copy((const AtlasCopyDesc *)c->copy_descs.ptr, m, total, (uint32_t *)c->atlas.ptr, c->atlas_w, c->upload_stream);
+    HIP_TRY(c, hipGetLastError());
+    // every frame enqueued from here on runs behind the copy (prepare_frame), and so does the caller's later work on src_stream
+    HIP_TRY(c, hipEventRecord(c->atlas_ready, c->upload_stream));
+    c->atlas_epoch += 1u;
+    if (src_stream) HIP_TRY(c, hipStreamWaitEvent((hipStream_t)src_stream, c->atlas_ready, 0));
     return VELLO_HIP_OK;
 }
 

@@ -171,7 +171,7 @@ void *vh_brush_image(uint64_t id, uint32_t width, uint32_t height, uint32_t form
     b.image.height = height;
     b.image.format = (vello_encoding::ImageFormat)format;
     b.image.alpha_type = (vello_encoding::ImageAlphaType)alpha_type;
-    b.image.data = std::make_shared<const std::vector<uint8_t>>(rgba8, rgba8 + (size_t)width * height * 4u);
+    if (rgba8) b.image.data = std::make_shared<const std::vector<uint8_t>>(rgba8, rgba8 + (size_t)width * height * 4u);  // NULL: pixel-less (override_image)
     b.sampler.x_extend = (vello_encoding::Extend)x_extend;
     b.sampler.y_extend = (vello_encoding::Extend)y_extend;
     b.sampler.quality = (vello_encoding::ImageQuality)quality;
@@ -259,6 +259,8 @@ const uint8_t *vh_resolver_upload(void *r, uint32_t i, uint32_t xywh_out[4]) {
     xywh_out[3] = u.image.height;
     return u.image.data ? u.image.data->data() : nullptr;
 }
+// the image id of upload i of the last resolve (a pixel-less upload: vh_resolver_upload returns NULL)
+uint64_t vh_resolver_upload_id(void *r, uint32_t i) { return (*((ResolverHandle *)r)->last.uploads)[i].image.id; }
 
 // stream access: 0 path_tags(u8) 1 path_data(u32) 2 draw_tags(u32) 3 draw_data(u32) 4 transforms(6 f32) 5 styles(2 u32)
 size_t vh_scene_stream_bytes(void *s, int which) {
@@ -339,6 +341,34 @@ int vh_renderer_render_to_texture(void *r, void *scene, void *texture, size_t st
     p.height = height;
     p.antialiasing_method = (vello::AaConfig)aa;
     return ((vello::Renderer *)r)->render_to_texture(((SceneHandle *)scene)->scene, texture, stride, is_device != 0, p);
+}
+// render_to_texture with the stream that writes the override sources (nullable hipStream_t)
+int vh_renderer_render_to_texture_on(void *r, void *scene, void *texture, size_t stride, int is_device, uint32_t width, uint32_t height,
+                                     const float *base_color, uint32_t aa, void *src_stream) {
+    vello::RenderParams p;
+    p.base_color = color_from(base_color);
+    p.width = width;
+    p.height = height;
+    p.antialiasing_method = (vello::AaConfig)aa;
+    return ((vello::Renderer *)r)->render_to_texture(((SceneHandle *)scene)->scene, texture, stride, is_device != 0, p, src_stream);
+}
+// Renderer::override_image: has_source = 0 removes the override.  Returns 1 and the previous source in prev[0..1] if there was one.
+int vh_renderer_override_image(void *r, uint64_t image_id, int has_source, uint64_t src, uint64_t stride, uint64_t prev[2]) {
+    vello_encoding::ImageData image;
+    image.id = image_id;
+    std::optional<vello::DeviceImageSource> source;
+    if (has_source) source = vello::DeviceImageSource{src, stride};
+    std::optional<vello::DeviceImageSource> old = ((vello::Renderer *)r)->override_image(image, source);
+    if (old && prev) {
+        prev[0] = old->src;
+        prev[1] = old->stride;
+    }
+    return old ? 1 : 0;
+}
+void vh_renderer_mark_override_image_dirty(void *r, uint64_t image_id) {
+    vello_encoding::ImageData image;
+    image.id = image_id;
+    ((vello::Renderer *)r)->mark_override_image_dirty(image);
 }
 const char *vh_renderer_error(void *r) { return ((vello::Renderer *)r)->error().c_str(); }
 void *vh_renderer_engine(void *r) { return ((vello::Renderer *)r)->engine(); }

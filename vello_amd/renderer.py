@@ -6,8 +6,8 @@ import enum
 
 import numpy as np
 
-from ._lib import load_library, VelloHipError, Capacities, Bump, LayoutStruct, RenderParamsStruct
-from .scene import Color
+from ._lib import load_library, VelloHipError, Capacities, Bump, LayoutStruct, RenderParamsStruct, ImageCopyStruct
+from .scene import Color, ImageAlphaType, ImageData, ImageFormat
 
 
 class AaConfig(enum.IntEnum):
@@ -66,6 +66,37 @@ def _data_ptr(texture, width=None, height=None):
     return ptr, is_dev
 
 
+def _texture_source(source):
+    """(address, row stride in bytes, height, width) of an override source: an [H, W, 4] uint8 tensor on the GPU whose texels
+    are RGBA8 words (stride(2) == 1, stride(1) == 4; any row stride, so a slice of a larger tensor works).  A numpy array of
+    the same shape stands for device memory only in the SIMT-emulated build that the CPU tests load; the GPU build refuses it."""
+    if isinstance(source, np.ndarray):
+        if source.dtype != np.uint8 or source.ndim != 3 or source.shape[2] != 4 or source.strides[2] != 1 or source.strides[1] != 4:
+            raise ValueError("an override source is an [H, W, 4] uint8 array of RGBA8 words")
+        return source.ctypes.data, source.strides[0], source.shape[0], source.shape[1]
+    import torch
+
+    if (not isinstance(source, torch.Tensor) or source.dtype != torch.uint8 or source.dim() != 3 or source.shape[2] != 4
+            or source.stride(2) != 1 or source.stride(1) != 4):
+        raise ValueError("an override source is a torch.uint8 tensor of shape [H, W, 4] with stride(2) == 1 and stride(1) == 4")
+    if not source.is_cuda:
+        raise ValueError("an override source lives on the GPU")
+    return source.data_ptr(), source.stride(0), source.shape[0], source.shape[1]
+
+
+def _source_stream(stream):
+    """(hipStream_t for src_stream, relay) for a torch stream.  The null stream cannot be named through the C ABI (NULL there
+    means "no source stream"), so its work is relayed through a pool stream ordered behind it; the caller then makes the null
+    stream wait for the relay (relay = (null stream, pool stream)).  Device-side ordering only, no host wait."""
+    import torch
+
+    if stream.cuda_stream:
+        return stream.cuda_stream, None
+    pool = torch.cuda.Stream(device=stream.device)
+    pool.wait_stream(stream)
+    return pool.cuda_stream, (stream, pool)
+
+
 class Renderer:
     """Renderer::new + Renderer::render_to_texture.  Raises VelloHipError when no GPU is usable."""
 
@@ -76,6 +107,7 @@ class Renderer:
         self._h = self._lib.vh_renderer_new(options.device, options.antialiasing_support, _caps(options.capacities), err, 512)
         if not self._h:
             raise VelloHipError(err.value.decode() or "vello_hip_create failed")
+        self._overrides = {}  # image id -> source (the renderer keeps it alive, as upstream holds the wgpu::Texture)
 
     def __del__(self):
         try:
@@ -86,12 +118,54 @@ class Renderer:
         self._h = None
 
     def render_to_texture(self, scene, texture, params):
+        """Override sources are copied into the atlas in one batch behind the work already enqueued on torch's current stream,
+        which then waits for the copy (vello_hip_copy_images_device)."""
         ptr, is_dev = _data_ptr(texture, params.width, params.height)
         stride = params.width * 4
-        r = self._lib.vh_renderer_render_to_texture(self._h, scene._h, ptr, stride, 1 if is_dev else 0, params.width,
-                                                    params.height, params.base_color._ptr(), int(params.antialiasing_method))
+        src_stream = relay = None
+        if any(not isinstance(t, np.ndarray) for t in self._overrides.values()):
+            import torch
+
+            src_stream, relay = _source_stream(torch.cuda.current_stream())
+        r = self._lib.vh_renderer_render_to_texture_on(self._h, scene._h, ptr, stride, 1 if is_dev else 0, params.width, params.height,
+                                                       params.base_color._ptr(), int(params.antialiasing_method), src_stream)
+        if relay is not None:
+            relay[0].wait_stream(relay[1])
         if r != 0:
             raise VelloHipError(f"render_to_texture failed ({r}): {self._lib.vh_renderer_error(self._h).decode()}")
+
+    def override_image(self, image, source):
+        """Renderer::override_image (lib.rs:536-545): whenever `image` is scheduled for upload into the atlas, its texels are
+        copied from `source` (an [H, W, 4] RGBA8 tensor on the GPU of the image's size; see _texture_source) instead of its
+        pixels; None removes the override.  Marks the image dirty.  Returns the previous source or None."""
+        if source is not None:
+            addr, row_stride, h, w = _texture_source(source)
+            if (h, w) != (image.height, image.width):
+                raise ValueError(f"override source is {w}x{h}, the image {image.width}x{image.height}")
+            self._lib.vh_renderer_override_image(self._h, ctypes.c_uint64(image.id), 1, addr, row_stride, None)
+        else:
+            self._lib.vh_renderer_override_image(self._h, ctypes.c_uint64(image.id), 0, 0, 0, None)
+        previous = self._overrides.pop(image.id, None)
+        if source is not None:
+            self._overrides[image.id] = source
+        return previous
+
+    def mark_override_image_dirty(self, image):
+        """Renderer::mark_override_image_dirty (lib.rs:547-555): the source's contents changed; the next render that uses the
+        image copies it again (otherwise the atlas keeps the texels of the last copy)."""
+        self._lib.vh_renderer_mark_override_image_dirty(self._h, ctypes.c_uint64(image.id))
+
+    def register_texture(self, texture):
+        """Renderer::register_texture (lib.rs:557-604): a pixel-less Rgba8 / straight-alpha ImageData of the texture's size with
+        the texture as its override."""
+        _, _, h, w = _texture_source(texture)
+        image = ImageData.empty(w, h, ImageFormat.Rgba8, ImageAlphaType.Alpha)
+        self.override_image(image, texture)
+        return image
+
+    def unregister_texture(self, image):
+        """Renderer::unregister_texture (lib.rs:606-609)."""
+        self.override_image(image, None)
 
     def last_bump(self):
         b = Bump()
@@ -145,12 +219,49 @@ class Engine:
         h, w = pixels.shape[:2]
         self._check(self._lib.vello_hip_write_image(self._h, x, y, w, h, pixels.ctypes.data, w * 4), "write_image")
 
-    def upload_resolved(self, resolved):
-        """Everything a Resolver result carries: atlas (re)creation + image writes, ramps, packed scene."""
+    def copy_images_device(self, copies, stream=None):
+        """vello_hip_copy_images_device: `copies` are (x, y, width, height, address, row stride in bytes) entries, copied into the
+        atlas by one kernel launch.  The entries of a call are copied concurrently: their destinations must not overlap, and no
+        source may lie in the atlas.  Calls are ordered among themselves and against frames (behind the frames enqueued before,
+        in front of those enqueued after).  An address is an int or an array / tensor (its first texel).  `stream`
+        (a hipStream_t as an int, or a torch stream -- torch's default stream included) is the stream that writes the sources: the
+        copy runs behind it, and it waits for the copy.  Returns without waiting."""
+        arr = (ImageCopyStruct * max(len(copies), 1))()
+        for i, (x, y, w, h, addr, row_stride) in enumerate(copies):
+            if hasattr(addr, "data_ptr"):
+                addr = addr.data_ptr()
+            elif isinstance(addr, np.ndarray):
+                addr = addr.ctypes.data
+            arr[i] = ImageCopyStruct(int(addr or 0), int(row_stride), int(x), int(y), int(w), int(h))
+        relay = None
+        if hasattr(stream, "cuda_stream"):
+            s, relay = _source_stream(stream)
+        else:
+            s = stream
+        r = self._lib.vello_hip_copy_images_device(self._h, arr, len(copies), ctypes.c_void_p(int(s)) if s else None)
+        if relay is not None:
+            relay[0].wait_stream(relay[1])
+        self._check(r, "copy_images_device")
+
+    def upload_resolved(self, resolved, sources=None):
+        """Everything a Resolver result carries: atlas (re)creation + image writes, ramps, packed scene.  Pixel-less images
+        (resolved.device_uploads) are copied from `sources` ({image id: device source, as override_image takes}) in one
+        copy_images_device batch; one without a source is refused, as Renderer refuses it, before anything is uploaded."""
+        missing = [i for _, _, _, _, i in resolved.device_uploads if sources is None or i not in sources]
+        if missing:
+            raise VelloHipError(f"Tried to draw an invalid empty image (id {missing[0]}): no source for a pixel-less image")
         if resolved.atlas_size:
             self.resize_image_atlas(resolved.atlas_size, resolved.atlas_size)
             for x, y, px in resolved.uploads:
                 self.write_image(x, y, px)
+            if resolved.device_uploads:
+                copies = []
+                for x, y, w, h, i in resolved.device_uploads:
+                    addr, row_stride, sh, sw = _texture_source(sources[i])
+                    if (sh, sw) != (h, w):
+                        raise ValueError(f"source of image {i} is {sw}x{sh}, the image {w}x{h}")
+                    copies.append((x, y, w, h, addr, row_stride))
+                self.copy_images_device(copies)
         self.upload_scene(resolved.packed, resolved.layout, resolved.ramps)
 
     def render_frame(self, packed, layout, width, height, base_color, aa, out=None, ramps=None):

@@ -158,6 +158,18 @@ class ImageData:
         self.id = _next_image_id[0]
         _next_image_id[0] += 1
 
+    @classmethod
+    def empty(cls, width, height, format=ImageFormat.Rgba8, alpha_type=ImageAlphaType.Alpha):
+        """A pixel-less image (upstream: an ImageData over an empty blob, lib.rs:580-592): its texels come from the device
+        source Renderer.override_image binds to it.  Rendering it without one fails (wgpu_engine.rs:505-514)."""
+        im = cls.__new__(cls)
+        im.pixels = None
+        im.width, im.height = int(width), int(height)
+        im.format, im.alpha_type = ImageFormat(format), ImageAlphaType(alpha_type)
+        im.id = _next_image_id[0]
+        _next_image_id[0] += 1
+        return im
+
 
 class ImageBrush:
     """peniko::ImageBrush = ImageData + ImageSampler {x_extend, y_extend, quality, alpha}."""
@@ -168,7 +180,8 @@ class ImageBrush:
 
     def _handle(self):
         im = self.image
-        return _BrushHandle(load_library().vh_brush_image(im.id, im.width, im.height, int(im.format), int(im.alpha_type), im.pixels.ctypes.data,
+        px = None if im.pixels is None else im.pixels.ctypes.data
+        return _BrushHandle(load_library().vh_brush_image(im.id, im.width, im.height, int(im.format), int(im.alpha_type), px,
                                                           int(self.x_extend), int(self.y_extend), int(self.quality), self.alpha))
 
 
@@ -313,22 +326,28 @@ class Scene:
 
 class Resolved:
     """What Resolver::resolve returns (resolve.rs:172-180): packed scene + Layout, the ramp texture and the image atlas
-    work list [(x, y, HxWx4 uint8 pixels)]."""
+    work list [(x, y, HxWx4 uint8 pixels)].  Pixel-less images (ImageData.empty) are listed apart, in `device_uploads`
+    [(x, y, width, height, image id)]: their texels come from an override source."""
 
-    def __init__(self, packed, layout, ramps, atlas_size, atlas_resized, uploads):
+    def __init__(self, packed, layout, ramps, atlas_size, atlas_resized, uploads, device_uploads=()):
         self.packed, self.layout, self.ramps = packed, layout, ramps
         self.atlas_size, self.atlas_resized, self.uploads = atlas_size, atlas_resized, uploads
+        self.device_uploads = list(device_uploads)
 
     def __iter__(self):  # (packed, layout) unpacking, like Scene.resolve()
         return iter((self.packed, self.layout))
 
-    def atlas_image(self):
-        """The full atlas as an array (for the oracle, which takes the atlas whole)."""
+    def atlas_image(self, sources=None):
+        """The full atlas as an array (for the oracle, which takes the atlas whole).  `sources` ({image id: HxWx4 array}) fills
+        the places of pixel-less images; those without one stay zero."""
         if not self.atlas_size:
             return None
         a = np.zeros((self.atlas_size, self.atlas_size, 4), dtype=np.uint8)
         for x, y, px in self.uploads:
             a[y:y + px.shape[0], x:x + px.shape[1]] = px
+        for x, y, w, h, image_id in self.device_uploads:
+            if sources is not None and image_id in sources:
+                a[y:y + h, x:x + w] = np.asarray(sources[image_id], dtype=np.uint8)[:h, :w]
         return a
 
 
@@ -368,11 +387,15 @@ class Resolver:
             xywh = (ctypes.c_uint32 * 4)()
             dp = self._lib.vh_resolver_upload(self._h, i, xywh)
             x, y, w, h = list(xywh)
-            px = np.ctypeslib.as_array(ctypes.cast(dp, ctypes.POINTER(ctypes.c_uint8)), shape=(h, w, 4)).copy()
+            if dp:
+                entry = np.ctypeslib.as_array(ctypes.cast(dp, ctypes.POINTER(ctypes.c_uint8)), shape=(h, w, 4)).copy()
+            else:  # a pixel-less image: an override source supplies it
+                entry = (w, h, int(self._lib.vh_resolver_upload_id(self._h, i)))
             self._resident.pop((x, y), None)  # a later upload paints over earlier ones: keep the list in upload order
-            self._resident[(x, y)] = px
-        uploads_all = [(x, y, px) for (x, y), px in self._resident.items()]
-        r = Resolved(packed, Layout(*list(lay)), ramps, atlas_size, atlas_resized, uploads_all)
+            self._resident[(x, y)] = entry
+        uploads_all = [(x, y, e) for (x, y), e in self._resident.items() if isinstance(e, np.ndarray)]
+        device_all = [(x, y) + e for (x, y), e in self._resident.items() if not isinstance(e, np.ndarray)]
+        r = Resolved(packed, Layout(*list(lay)), ramps, atlas_size, atlas_resized, uploads_all, device_all)
         r.new_uploads = n_uploads
         r.evicted = int(info[4])
         return r
