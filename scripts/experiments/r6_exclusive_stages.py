@@ -1,7 +1,10 @@
 """Round 6: stages that run for ONE frame at a time while frames are in flight (VELLO_HIP_DEBUG_EXCLUSIVE_SHIFT: the stage's launches wait
 for the same stage of the frame enqueued before).  Two kernels of the same kind share the chip worst (both issue-bound, or both
 bandwidth-bound: DESIGN 6.3's batching estimate); does keeping k_fine / k_path_count / ... exclusive spread the frames' phases for good?
-d2 (WORKLOAD=...), frames/s with four in flight per set of exclusive stages, alternating with none.  (profiles/r06_exclusive_stages.txt)"""
+d2 (WORKLOAD=...), frames/s with four in flight per set of exclusive stages, alternating with none.  (profiles/r06_exclusive_stages.txt)
+
+NEEDS the tree's library built with scripts/experiments/exclusive_stages.patch applied (patch -p1, then __graft_entry__.build()): the
+product library ignores debug bits it does not know, so against it every set of stages measures the same frames as none."""
 import os
 import sys
 import time

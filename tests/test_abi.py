@@ -52,6 +52,54 @@ def test_product_never_imports_oracle():
                 assert "simt_emu" not in text or f == "_lib.py", f
 
 
+def listed_kernels():
+    """KERNELS of vello_amd/csrc/sources.mk: the engine/<name>.hip sources the library is built from."""
+    text = open(os.path.join(ROOT, "vello_amd", "csrc", "sources.mk")).read()
+    return re.search(r"^KERNELS\s*=(.*)$", text, flags=re.M).group(1).split()
+
+
+def test_engine_tree_holds_only_built_sources():
+    # every file under csrc/engine/ is a KERNELS source or reached by #include "..." from one: a copy of a kernel that the build
+    # never compiles cannot sit beside the built ones (nor feed kernel_sources_hash()'s headers)
+    engine = os.path.join(ROOT, "vello_amd", "csrc", "engine")
+    todo, reached = [os.path.join(engine, k + ".hip") for k in listed_kernels()], set()
+    while todo:
+        f = os.path.normpath(todo.pop())
+        if f not in reached:
+            reached.add(f)
+            text = open(f).read()
+            todo += [os.path.join(os.path.dirname(f), inc) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, flags=re.M)]
+    present = {os.path.normpath(os.path.join(d, f)) for d, _, files in os.walk(engine) for f in files}
+    assert sorted(present - reached) == []
+
+
+def test_kernel_sources_hash_covers_what_is_built(tmp_path):
+    # bench.py's roofline.traffic_stale: on a copy of the tree, a stray engine/*.hip leaves the hash as it is, an edit to a listed
+    # source or a missing public header moves it
+    import importlib.util
+    import shutil
+
+    from vello_amd._lib import kernel_sources_hash
+
+    shutil.copytree(os.path.join(ROOT, "vello_amd", "csrc"), tmp_path / "vello_amd" / "csrc", ignore=shutil.ignore_patterns("build"))
+    shutil.copy(os.path.join(ROOT, "vello_amd", "_lib.py"), tmp_path / "vello_amd")
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    spec = importlib.util.spec_from_file_location("lib_copy", tmp_path / "vello_amd" / "_lib.py")
+    copy = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(copy)
+    engine = tmp_path / "vello_amd" / "csrc" / "engine"
+    h0 = copy.kernel_sources_hash()
+    assert h0 == kernel_sources_hash()
+    (engine / "x.hip").write_text((engine / "fine.hip").read_text() + "// a stray copy\n")
+    assert copy.kernel_sources_hash() == h0
+    listed = engine / (listed_kernels()[-1] + ".hip")
+    listed.write_text(listed.read_text() + "// edited\n")
+    h1 = copy.kernel_sources_hash()
+    assert h1 != h0
+    os.remove(tmp_path / "include" / "vello_hip.h")
+    assert copy.kernel_sources_hash() not in (h0, h1)
+
+
 def test_mask_luts_match_oracle(built):
     import numpy as np
 

@@ -177,22 +177,32 @@ def load_library():
 
 
 def kernel_sources_hash():
-    """sha1 over the kernel sources (vello_amd/csrc/engine/*, csrc/Makefile): what a profile or a PMC pass says it measured.  A
-    commit hash moves with every documentation commit and does not exist on the GPU box; this says whether the KERNELS are the ones
-    the numbers came from (bench.py: roofline.traffic_stale)."""
+    """sha1 over what the kernel objects are built from: what a profile or a PMC pass says it measured.  A commit hash moves with
+    every documentation commit and does not exist on the GPU box; this says whether the KERNELS are the ones the numbers came
+    from (bench.py: roofline.traffic_stale)."""
     import hashlib
     import os
 
     here = os.path.dirname(os.path.abspath(__file__))
     root = os.path.join(here, "csrc")
-    h = hashlib.sha1()
-    # an explicit list (ADVICE r5): the Makefile, every source the kernel objects depend on -- engine/*.hip, *.h, *.inc and the
-    # public header with the layout / config / flag types the kernels use -- and nothing else (no editor backups, no stray files)
     engine = os.path.join(root, "engine")
-    files = [os.path.join(root, "Makefile"), os.path.join(os.path.dirname(here), "include", "vello_hip.h")]
-    files += sorted(os.path.join(engine, f) for f in os.listdir(engine) if f.endswith((".hip", ".h", ".inc")))
+    # the Makefile and sources.mk, the KERNELS sources sources.mk names, every header they may include (engine/*.h, *.inc) and the
+    # public header with the layout / config / flag types the kernels use -- nothing that is not built (no stray files, no backups)
+    with open(os.path.join(root, "sources.mk")) as fh:
+        kernels = next(line.split("=", 1)[1].split() for line in fh if line.split("=", 1)[0].strip() == "KERNELS")
+    files = [os.path.join(root, "Makefile"), os.path.join(root, "sources.mk")]
+    files += [os.path.join(engine, k + ".hip") for k in kernels]
+    files += sorted(os.path.join(engine, f) for f in os.listdir(engine) if f.endswith((".h", ".inc")))
+    h = hashlib.sha1()
     for f in files:
         with open(f, "rb") as fh:
             h.update(os.path.basename(f).encode())
             h.update(fh.read())
+    header = os.path.join(os.path.dirname(here), "include", "vello_hip.h")
+    if os.path.isfile(header):
+        with open(header, "rb") as fh:
+            h.update(b"vello_hip.h")
+            h.update(fh.read())
+    else:  # (a layout without the repository's include/: still a hash, and not one of a tree that has the header)
+        h.update(b"vello_hip.h: absent")
     return h.hexdigest()[:12]

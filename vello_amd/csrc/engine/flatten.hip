@@ -514,11 +514,7 @@ __device__ void flatten_euler_coop(Emitter &em, EulerCoopLds &cl, bool valid, co
     // inputs walk alone in any case.
     {
         const unsigned long long m_valid = __ballot(valid), m_two = __ballot(valid && two_sided);
-#ifdef VK_FL_NO_COOP  // (sweep switch: every lane on its own, always)
-        const bool alone = true;
-#else
         const bool alone = !few_entries && (uint32_t)__popcll(m_two) * 2u < (uint32_t)__popcll(m_valid);
-#endif
         if (valid && (alone || !tame)) {
             flatten_euler(em, cubic, path_ix, local_to_device, offset, start_p, end_p, two_sided, start_n, end_n);
             active = false;
