@@ -233,6 +233,29 @@ uint64_t vello_hip_fused_launches(vello_hip_ctx *ctx);
 int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                                   const vello_hip_render_params *params, vello_hip_capacities *out);
 
+/* Viewport culling (default 0: every buffer and counter is the reference's).  With it on, flatten leaves out of the line soup
+ * every line that lies wholly off the target on its top, bottom or right side.  With wt = ceil(width / 16), ht = ceil(height / 16)
+ * and S = 0.0625f, a line (p0, p1) is left out iff, in f32,
+ *     p0.y * S >= ht && p1.y * S >= ht,  or  p0.y * S <= 0 && p1.y * S <= 0,  or  p0.x * S >= wt && p1.x * S >= wt
+ * (a NaN coordinate fails its comparisons: the line stays).  Lines wholly LEFT of the target stay: they bump the backdrops of
+ * their rows.  path_count drops exactly these lines before it touches a backdrop or a count (path_count.wgsl:103-164: a path's
+ * tile box is its draw box cut to the target), so
+ *   1. path boxes -- hence draw boxes, clip boxes, bin lists, Path records, bump.binning, bump.tile -- do not change: a path's
+ *      box is still the union of ALL its lines;
+ *   2. the soup holds the lines the rule keeps and bump.lines counts them.  Exception: a curve piece too large for a workgroup's
+ *      staging area has its slots reserved before its lines exist and keeps all of them (then: kept lines <= soup <= all lines,
+ *      bump.lines = the soup's size);
+ *   3. everything behind the soup is unchanged: backdrops, segment counts, bump.seg_counts, bump.segments, the PTCL, the
+ *      segments, the image (seg_counts[].line_ix indexes the smaller soup);
+ *   4. the line pool overflows (VELLO_HIP_E_CAPACITY, auto-grow's demand) on the smaller count: a view of a large scene fits a
+ *      pool that the whole scene overflows.
+ * vello_hip_estimate_capacities is unchanged (still an upper bound).  Applies to frames enqueued after the call, on every entry
+ * point that renders (render, render_frame, render_resident, run_stages with FLATTEN in the range) and on all in-flight buffer
+ * sets; frames already enqueued keep the setting they were enqueued with.  Worth switching on when a good part of the scene
+ * lies off the target (a zoomed or panned view); on a scene that is all on the target flatten pays the test for nothing.
+ * VELLO_HIP_E_INVALID for a null context. */
+int vello_hip_set_viewport_cull(vello_hip_ctx *ctx, int enabled);
+
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a
  * later opaque full-tile cover is normally not emitted; the image is the same, but bump.segments / bump.ptcl and the
  * PTCL words are then <= the reference's): with it set, PTCL, segment slices and every bump counter equal the

@@ -85,6 +85,13 @@ impl HipRenderer {
         Ok(Self { ctx, resolver: Resolver::new(), packed: Vec::new(), atlas_size: (0, 0), overrides: HashMap::new() })
     }
 
+    /// `vello_hip_set_viewport_cull`: flatten leaves the lines that lie wholly off the target's top, bottom or right side out
+    /// of the line soup (the image does not change; `include/vello_hip.h` has the rule).  Off by default; applies to the
+    /// frames rendered after the call.
+    pub fn set_viewport_cull(&mut self, enabled: bool) {
+        unsafe { vello_hip_set_viewport_cull(self.ctx, enabled as c_int) };
+    }
+
     /// `Renderer::override_image` (vello/src/lib.rs:536-545): whenever the resolver schedules `image` for upload, its texels
     /// are copied from `texture` (device to atlas, batched with the frame's other overrides) instead of its blob; `None`
     /// removes the override.  Marks the image dirty; returns the previous source.

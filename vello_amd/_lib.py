@@ -93,6 +93,7 @@ def load_library():
     sig("vello_hip_get_capacities", i32, [vp, c.POINTER(Capacities)])
     sig("vello_hip_grow_pools", i32, [vp, c.POINTER(Bump), c.POINTER(Capacities)])
     sig("vello_hip_set_auto_grow", i32, [vp, i32])
+    sig("vello_hip_set_viewport_cull", i32, [vp, i32])
     sig("vello_hip_set_debug_flags", i32, [vp, u32])
     sig("vello_hip_last_render_attempts", u32, [vp])
     sig("vello_hip_fused_launches", ctypes.c_uint64, [vp])

@@ -183,6 +183,7 @@ struct Frame {
     bool flatten_coop;          // flatten's heavy list by the kernels of the wave-cooperative walk (flatten_walk.inc) instead of round 4's
     bool sequential_clip;  // VELLO_HIP_DEBUG_SEQ_CLIP: the one-wave stack machine whatever the clip count
     bool no_cull;  // VELLO_HIP_DEBUG_NO_CULL: coarse emits every draw, as the reference does (exact PTCL / segment diffs)
+    bool viewport_cull;  // vello_hip_set_viewport_cull: flatten leaves lines off the target's top, bottom and right out of the soup (flatten.hip)
     bool brushes;  // the scene has gradient / image / blurred-rect draw objects (selects fine's specialisation)
     const uint32_t *mask_lut8;
     const uint32_t *mask_lut16;

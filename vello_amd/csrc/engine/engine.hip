@@ -155,6 +155,7 @@ struct vello_hip_ctx {
     uint32_t n_active = 1;  // lanes in the rotation (<= lanes.size(): shrinking keeps the buffers)
     uint32_t next_lane = 0, last_lane = 0;
     bool auto_grow = false;
+    bool viewport_cull = false;  // vello_hip_set_viewport_cull: copied into every Frame when it is prepared
     hipStream_t copy_stream = nullptr;  // vello_hip_gather_frames: this context's peer copy
     hipEvent_t frame_done = nullptr;
     // vello_hip_write_image: atlas uploads are stream-ordered, not host-synchronous (wgpu's queue.write_texture is queued
@@ -506,6 +507,7 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
     f.n_ramps = sc.n_ramps;
     f.brushes = sc.brushes || c->force_brushes;
     f.no_cull = (c->debug_flags & VELLO_HIP_DEBUG_NO_CULL) != 0u;
+    f.viewport_cull = c->viewport_cull;
     f.sequential_clip = (c->debug_flags & VELLO_HIP_DEBUG_SEQ_CLIP) != 0u;
     f.stroke_kernel_min_lines = (c->debug_flags & VELLO_HIP_DEBUG_STROKE_KERNEL) != 0u ? 0u : FLATTEN_STROKE_KERNEL_MIN_LINES;
     f.path_count_small = sc.soup_lines >= 0 && sc.soup_lines < PATH_COUNT_SMALL_MAX_LINES;
@@ -1414,6 +1416,15 @@ int vello_hip_set_debug_flags(vello_hip_ctx *c, uint32_t flags) {
 int vello_hip_set_auto_grow(vello_hip_ctx *c, int enabled) {
     if (!c) return VELLO_HIP_E_INVALID;
     c->auto_grow = enabled != 0;
+    return VELLO_HIP_OK;
+}
+
+// A frame takes the setting when it is prepared (Frame::viewport_cull travels to flatten's kernels by value), so frames already
+// enqueued keep theirs.  The scene's remembered soup size (SceneSlot::soup_lines) only picks path_count's chunk size -- its grid
+// strides over the pool -- so a frame after a toggle is at worst cut into the other chunk size once.
+int vello_hip_set_viewport_cull(vello_hip_ctx *c, int enabled) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    c->viewport_cull = enabled != 0;
     return VELLO_HIP_OK;
 }
 

@@ -155,7 +155,7 @@ struct FlattenShared {
     float p0x[CAP], p0y[CAP], p1x[CAP], p1y[CAP];
     uint32_t count;    // slots handed out (may run past the capacity)
     uint32_t lds_end;  // first slot of the first piece that did not fit (dense prefix [0, lds_end) is staged)
-    uint32_t base;
+    uint32_t base;     // where the staged lines go in the soup; zero between flushes (viewport culling sums its waves' survivors here first)
 };
 
 struct Emitter {
@@ -248,19 +248,100 @@ __device__ __forceinline__ void copy_staged_lines(const FlattenShared<CAP> &sh, 
     }
 }
 
+// ---- viewport culling (vello_hip_set_viewport_cull) ---------------------------------------------------------------------
+// A line wholly at or below the target's bottom edge, at or above its top edge, or at or right of its right edge crosses no
+// tile of its path: the path's tile box is its draw box cut to the target, and path_count leaves such a line before it touches
+// a backdrop or a count (path_count.wgsl:103-164).  Lines LEFT of the target stay: they bump the backdrops of their rows.  The
+// comparisons are path_count's own -- the ends times TILE_SCALE against the target in tiles -- and false for a NaN: kept.
+// The test sits at the three flush sites, on the staged records, never in the walk: the paths' boxes are still the union of ALL
+// lines.  A piece that bypassed the staging area (Emitter::alloc, LINE_IX_GLOBAL) had its slots before its lines existed and
+// keeps them all.
+__device__ __forceinline__ bool line_off_target(float p0x, float p0y, float p1x, float p1y, float wt, float ht) {
+    const float S = 0.0625f;
+    const float x0 = p0x * S, y0 = p0y * S, x1 = p1x * S, y1 = p1y * S;
+    return (y0 >= ht && y1 >= ht) || (y0 <= 0.0f && y1 <= 0.0f) || (x0 >= wt && x1 >= wt);
+}
+
+// First half of a culling flush (all threads, behind the barrier that ends the emits): every wave counts the survivors of ITS
+// share of the staged records [0, n_lds) -- wave w tests records w * 64 + 256 r + lane -- and adds the count to sh.base (zero
+// between flushes) with one LDS atomic, whose answer is where the wave's survivors start among the workgroup's.  Behind the
+// next barrier sh.base is the number of slots to reserve.
+template <uint32_t CAP>
+__device__ __forceinline__ uint32_t cull_count_staged(FlattenShared<CAP> &sh, uint32_t n_lds, float wt, float ht, uint32_t tid) {
+    const uint32_t lane = tid & 63u;
+    uint32_t n_wave = 0u;
+    for (uint32_t i0 = tid - lane; i0 < n_lds; i0 += 256u) {  // (wave-uniform bounds)
+        const uint32_t i = i0 + lane;
+        const bool keep = i < n_lds && !line_off_target(sh.p0x[i], sh.p0y[i], sh.p1x[i], sh.p1y[i], wt, ht);
+        n_wave += (uint32_t)__popcll(__ballot(keep));
+    }
+    uint32_t off = 0u;
+    if (lane == 0u && n_wave != 0u) off = atomicAdd(&sh.base, n_wave);
+    return (uint32_t)__shfl((int)off, 0);
+}
+
+// Second half: the survivors, densely, from `first` (= the workgroup's reservation + the wave's offset) on.  A wave's survivors
+// of a round are consecutive records stored by consecutive (surviving) lanes; the running offset is a register.
+template <uint32_t CAP>
+__device__ __forceinline__ void copy_kept_lines(const FlattenShared<CAP> &sh, LineSoup *lines, uint32_t lines_size, uint32_t first, uint32_t n_lds,
+                                                float wt, float ht, uint32_t tid) {
+    const uint32_t lane = tid & 63u;
+    uint32_t o = first;
+    for (uint32_t i0 = tid - lane; i0 < n_lds; i0 += 256u) {
+        const uint32_t i = i0 + lane;
+        LineSoup l;
+        l.path_ix = 0u; l.pad = 0u;
+        l.p0x = l.p0y = l.p1x = l.p1y = 0.0f;
+        bool keep = false;
+        if (i < n_lds) {
+            l.path_ix = sh.path_ix[i];
+            l.p0x = sh.p0x[i]; l.p0y = sh.p0y[i]; l.p1x = sh.p1x[i]; l.p1y = sh.p1y[i];
+            keep = !line_off_target(l.p0x, l.p0y, l.p1x, l.p1y, wt, ht);
+        }
+        const unsigned long long m = __ballot(keep);
+        const uint32_t at = o + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (keep && at < lines_size) lines[at] = l;
+        o += (uint32_t)__popcll(m);
+    }
+}
+
 // ONE atomicAdd(bump.lines) for the staged lines of the workgroup (the reference issues one per line), then a
 // coalesced copy: thread i writes the 24-byte record i.  Resets the staging area for the next round.
+// CULL: only the lines that pass line_off_target are counted, reserved and written.  A template parameter, as in every kernel of
+// this file (the host launches the <.., true> instantiations when the option is on): as a run-time branch at the flush the option
+// cost the default path 1 % of d2's frames/s through the heavy kernels' register allocation alone (profiles/viewport_cull.txt).
+// (out of line: the heavy kernels sit at 256 registers, and the walk around the flush keeps its allocation when this is a call)
 template <uint32_t CAP>
-__device__ __forceinline__ void flush_staged_lines(FlattenShared<CAP> &sh, Bump *bump, LineSoup *lines, uint32_t lines_size, uint32_t tid) {
+__device__ __attribute__((noinline)) void flush_kept_lines(FlattenShared<CAP> &sh, Bump *bump, LineSoup *lines, uint32_t lines_size, uint32_t n_lds,
+                                                           uint32_t width_in_tiles, uint32_t height_in_tiles) {
+    const uint32_t tid = threadIdx.x;
+    const float wt = (float)width_in_tiles, ht = (float)height_in_tiles;
+    const uint32_t wave_off = cull_count_staged(sh, n_lds, wt, ht, tid);
+    __syncthreads();
+    if (tid == 0u) {
+        const uint32_t kept = sh.base;
+        sh.base = kept ? atomicAdd(&bump->lines, kept) : 0u;
+    }
+    __syncthreads();
+    copy_kept_lines(sh, lines, lines_size, sh.base + wave_off, n_lds, wt, ht, tid);
+}
+
+template <bool CULL, uint32_t CAP>
+__device__ __forceinline__ void flush_staged_lines(FlattenShared<CAP> &sh, Bump *bump, LineSoup *lines, const Config &cfg, uint32_t tid) {
     __syncthreads();
     const uint32_t n_lds = minu(sh.count, sh.lds_end);
-    if (tid == 0u) sh.base = n_lds ? atomicAdd(&bump->lines, n_lds) : 0u;
-    __syncthreads();
-    copy_staged_lines(sh, lines, lines_size, sh.base, n_lds, tid);
+    if (CULL) {
+        flush_kept_lines(sh, bump, lines, cfg.lines_size, n_lds, cfg.width_in_tiles, cfg.height_in_tiles);
+    } else {
+        if (tid == 0u) sh.base = n_lds ? atomicAdd(&bump->lines, n_lds) : 0u;
+        __syncthreads();
+        copy_staged_lines(sh, lines, cfg.lines_size, sh.base, n_lds, tid);
+    }
     __syncthreads();
     if (tid == 0u) {
         sh.count = 0u;
         sh.lds_end = 0xffffffffu;
+        if (CULL) sh.base = 0u;
     }
     __syncthreads();
 }
@@ -1060,6 +1141,7 @@ __device__ __forceinline__ uint32_t flatten_tag_light(Emitter &em, const Config 
 }
 
 // (one workgroup of flatten's light pass: FLATTEN_BLOCK_TAGS tags from tag `block` x FLATTEN_BLOCK_TAGS on)
+template <bool CULL>
 __device__ __forceinline__ void flatten_light_workgroup(const Config &cfg, uint32_t block, uint32_t n_tags, const uint32_t *scene, const TagMonoid *tag_monoids,
                                                         PathBbox *path_bboxes, Control *control, LineSoup *lines, uint32_t *heavy_list) {
     __shared__ FlattenShared<FLATTEN_BLOCK_TAGS> sh;  // at most one line per tag: never overflows
@@ -1075,6 +1157,7 @@ __device__ __forceinline__ void flatten_light_workgroup(const Config &cfg, uint3
     if (tid == 0u) {
         sh.count = 0u;
         sh.lds_end = 0xffffffffu;
+        if (CULL) sh.base = 0u;
         sh_n_heavy[0] = sh_n_heavy[1] = sh_n_heavy[2] = 0u;
     }
     __syncthreads();
@@ -1118,17 +1201,25 @@ __device__ __forceinline__ void flatten_light_workgroup(const Config &cfg, uint3
     // The workgroup's four reservations -- its lines in the soup, its entries in the three lists -- as ONE instruction of four
     // lanes: a same-address atomic is a queue of every workgroup of the launch (12 ns each, 933 of them on the road map), and
     // the soup's after the copy-out, then the lists', were two such queues in a row on every workgroup's way out.
+    // (viewport culling: the lines it reserves are the survivors, counted first -- cull_count_staged)
     __syncthreads();
     const uint32_t n_lds = minu(sh.count, sh.lds_end);
+    const float cull_wt = (float)cfg.width_in_tiles, cull_ht = (float)cfg.height_in_tiles;
+    uint32_t wave_off = 0u;
+    if (CULL) {
+        wave_off = cull_count_staged(sh, n_lds, cull_wt, cull_ht, tid);
+        __syncthreads();
+    }
     if (tid < 4u) {
         uint32_t *const counter = tid == 0u ? &bump->lines : &control->heavy_count[tid - 1u];
-        const uint32_t n = tid == 0u ? n_lds : sh_n_heavy[tid - 1u];
+        const uint32_t n = tid == 0u ? (CULL ? sh.base : n_lds) : sh_n_heavy[tid - 1u];
         const uint32_t got = n ? atomicAdd(counter, n) : 0u;
         if (tid == 0u) sh.base = got;
         else sh_heavy_base[tid - 1u] = got;
     }
     __syncthreads();
-    copy_staged_lines(sh, lines, cfg.lines_size, sh.base, n_lds, tid);
+    if (CULL) copy_kept_lines(sh, lines, cfg.lines_size, sh.base + wave_off, n_lds, cull_wt, cull_ht, tid);
+    else copy_staged_lines(sh, lines, cfg.lines_size, sh.base, n_lds, tid);
     // curves fill heavy_list[0, n_tags), strokes [n_tags, 2 n_tags), stroked lines [2 n_tags, 3 n_tags) (the stroke workgroups
     // append the lines they hand on to [3 n_tags, 4 n_tags))
     for (uint32_t i = tid; i < sh_n_heavy[0]; i += 256u) heavy_list[sh_heavy_base[0] + i] = sh_heavy[i];
@@ -1140,6 +1231,7 @@ __device__ __forceinline__ void flatten_light_workgroup(const Config &cfg, uint3
 // the flatten workgroups fill the chip): they need the scene and what
 // k_pathtag_scan stored at the PATH markers, nothing of flatten's, and the stage as a launch of its own is 6-10 us of launch
 // boundary and look-back latency on the frame's critical path.
+template <bool CULL>
 __global__ void __launch_bounds__(256, 4) k_flatten_light(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
                                                           const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
                                                           Control *control, LineSoup *lines, uint32_t *heavy_list, uint32_t n_draw_blocks,
@@ -1149,7 +1241,7 @@ __global__ void __launch_bounds__(256, 4) k_flatten_light(Config cfg, uint32_t n
         draw_scan_workgroup(cfg, scene, control, draw_state, path_bboxes, draw_monoids, info, clip_inp);
         return;
     }
-    flatten_light_workgroup(cfg, blockIdx.x - n_draw_blocks, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list);
+    flatten_light_workgroup<CULL>(cfg, blockIdx.x - n_draw_blocks, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list);
 }
 
 // ---- stroked lines: flatten_tag's stroke branch without the Euler-spiral flattener ------------------------------
@@ -1323,7 +1415,7 @@ __device__ uint32_t g_stroke_tl_n;
 #else
 #define STL_STAMP(k) do { } while (0)
 #endif
-template <uint32_t CAP>
+template <bool CULL, uint32_t CAP>
 __device__ __forceinline__ void stroke_workgroup(FlattenShared<CAP> &sh, ArcQueue &arcs, uint32_t block, uint32_t n_blocks, const Config &cfg,
                                  uint32_t n_tags, const uint32_t *__restrict__ scene, const TagMonoid *__restrict__ tag_monoids,
                                  PathBbox *path_bboxes, Control *control, LineSoup *lines, uint32_t *heavy_list, uint32_t min_lines,
@@ -1335,6 +1427,7 @@ __device__ __forceinline__ void stroke_workgroup(FlattenShared<CAP> &sh, ArcQueu
     if (tid == 0u) {
         sh.count = 0u;
         sh.lds_end = 0xffffffffu;
+        if (CULL) sh.base = 0u;
         arcs.count = 0u;
     }
     __syncthreads();
@@ -1392,11 +1485,18 @@ __device__ __forceinline__ void stroke_workgroup(FlattenShared<CAP> &sh, ArcQueu
             const bool last_round = base + n_blocks * 256u >= n_lines_q;
             const bool do_flush = last_round || sh.count + FLATTEN_STROKE_ROUND_LINES > CAP;
             const uint32_t n_lds = do_flush ? minu(sh.count, sh.lds_end) : 0u;
+            // (viewport culling: a flush reserves the survivors, counted first -- cull_count_staged; sh.base is zero between flushes)
+            const float cull_wt = (float)cfg.width_in_tiles, cull_ht = (float)cfg.height_in_tiles;
+            uint32_t wave_off = 0u;
+            if (CULL && do_flush) {
+                wave_off = cull_count_staged(sh, n_lds, cull_wt, cull_ht, tid);
+                __syncthreads();
+            }
             // (the paths' boxes between the reservations' request and their answer: the box atomics need neither -- round 6)
             uint32_t got = 0u;
             if (tid < 2u) {
                 uint32_t *const counter = tid == 0u ? &control->arc_count[shard] : &bump->lines;
-                const uint32_t n = tid == 0u ? n_arcs : n_lds;
+                const uint32_t n = tid == 0u ? n_arcs : (CULL ? sh.base : n_lds);
                 got = n ? atomicAdd(counter, n) : 0u;
             }
             wave_bbox_update(path_bboxes, cfg.layout.n_paths, key, x0, y0, x1, y1, (int)lane);
@@ -1410,7 +1510,10 @@ __device__ __forceinline__ void stroke_workgroup(FlattenShared<CAP> &sh, ArcQueu
             STL_STAMP(4);
             // (a shard holds <= 256 arcs per round of each of its workgroups: arc_shard_cap is sized for that)
             if (tid < n_arcs && arcs.base + tid < arc_shard_cap) reinterpret_cast<ArcItem *>(arc_items)[shard * arc_shard_cap + arcs.base + tid] = arcs.item[tid];
-            if (do_flush) copy_staged_lines(sh, lines, cfg.lines_size, sh.base, n_lds, tid);
+            if (do_flush) {
+                if (CULL) copy_kept_lines(sh, lines, cfg.lines_size, sh.base + wave_off, n_lds, cull_wt, cull_ht, tid);
+                else copy_staged_lines(sh, lines, cfg.lines_size, sh.base, n_lds, tid);
+            }
 #ifdef VELLO_STROKE_TIMELINE
             __builtin_amdgcn_s_waitcnt(0);
 #endif
@@ -1430,6 +1533,7 @@ __device__ __forceinline__ void stroke_workgroup(FlattenShared<CAP> &sh, ArcQueu
                 if (do_flush) {
                     sh.count = 0u;
                     sh.lds_end = 0xffffffffu;
+                    if (CULL) sh.base = 0u;
                 }
             }
             __syncthreads();  // (the next round appends to both)
@@ -1448,7 +1552,7 @@ constexpr uint32_t HEAVY_FIRST = 1u, HEAVY_SET_ASIDE = 2u;
 #define VK_FL_LPW_DIV 1024u          // a long list is spread over this many waves ...
 #define VK_FL_LPW_DIV_STROKES 3072u  // ... a list with many stroked curves over this many (sweep constants)
 #endif
-template <uint32_t LISTS, bool COOP>
+template <uint32_t LISTS, bool COOP, bool CULL>
 __device__ __forceinline__ void heavy_workgroups(FlattenShared<FLATTEN_LDS_LINES> &sh, EulerCoopLds *coop, uint32_t block, uint32_t n_blocks, const Config &cfg, uint32_t n_tags,
                                                  const uint32_t *__restrict__ scene, const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
                                                  Control *control, LineSoup *lines, const uint32_t *__restrict__ heavy_list,
@@ -1489,6 +1593,7 @@ __device__ __forceinline__ void heavy_workgroups(FlattenShared<FLATTEN_LDS_LINES
     if (tid == 0u) {
         sh.count = 0u;
         sh.lds_end = 0xffffffffu;
+        if (CULL) sh.base = 0u;
     }
     __syncthreads();
     Bump *bump = &control->bump;
@@ -1558,13 +1663,13 @@ __device__ __forceinline__ void heavy_workgroups(FlattenShared<FLATTEN_LDS_LINES
         // list entries of one source workgroup keep tag order, so equal path keys still come in runs
         flp_mark(FLP_OTHER);
         wave_bbox_update(path_bboxes, cfg.layout.n_paths, key, x0, y0, x1, y1, (int)lane);
-        flush_staged_lines(sh, bump, lines, cfg.lines_size, tid);
+        flush_staged_lines<CULL>(sh, bump, lines, cfg, tid);
         flp_mark(FLP_BBOX_FLUSH);
     }
     flp_store();
 }
 
-template <bool COOP>
+template <bool COOP, bool CULL>
 __global__ void __launch_bounds__(256, 2) k_flatten_main(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
                                                          const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
                                                          Control *control, LineSoup *lines, uint32_t *heavy_list,
@@ -1573,23 +1678,24 @@ __global__ void __launch_bounds__(256, 2) k_flatten_main(Config cfg, uint32_t n_
     __shared__ __attribute__((aligned(16))) unsigned char smem[FLATTEN_MAIN_LDS];
     if (blockIdx.x < n_heavy_blocks) {
         // (the heavy workgroups keep their four waves' EulerCoopLds where the stroke workgroups keep their arc queue)
-        heavy_workgroups<HEAVY_FIRST, COOP>(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem), reinterpret_cast<EulerCoopLds *>(smem + FLATTEN_ARCS_AT),
+        heavy_workgroups<HEAVY_FIRST, COOP, CULL>(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem), reinterpret_cast<EulerCoopLds *>(smem + FLATTEN_ARCS_AT),
                                       blockIdx.x, n_heavy_blocks, cfg, n_tags, scene, tag_monoids,
                                       path_bboxes, control, lines, heavy_list, stroke_kernel_min_lines, arc_items, arc_shard_cap);
     } else {
-        stroke_workgroup(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem), *reinterpret_cast<ArcQueue *>(smem + FLATTEN_ARCS_AT),
+        stroke_workgroup<CULL>(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem), *reinterpret_cast<ArcQueue *>(smem + FLATTEN_ARCS_AT),
                          blockIdx.x - n_heavy_blocks, gridDim.x - n_heavy_blocks, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines,
                          heavy_list, stroke_kernel_min_lines, arc_items, arc_shard_cap);
     }
 }
 
+template <bool CULL>
 __global__ void __launch_bounds__(256, 2) k_flatten_tail(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
                                                          const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
                                                          Control *control, LineSoup *lines, const uint32_t *__restrict__ heavy_list,
                                                          const uint32_t *__restrict__ arc_items, uint32_t arc_shard_cap) {
     __shared__ FlattenShared<FLATTEN_LDS_LINES> sh;
     // (what the stroke workgroups set aside -- arcs, and lines that were not straight after all: every lane on its own)
-    heavy_workgroups<HEAVY_SET_ASIDE, false>(sh, nullptr, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, 0u, arc_items,
+    heavy_workgroups<HEAVY_SET_ASIDE, false, CULL>(sh, nullptr, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, 0u, arc_items,
                                       arc_shard_cap);
 }
 
@@ -1597,17 +1703,18 @@ __global__ void __launch_bounds__(256, 2) k_flatten_tail(Config cfg, uint32_t n_
 // two kinds side by side only matters to a frame that has the chip to itself, and its stroke workgroups hold the 256
 // registers and 76 KB its heavy ones need -- room the kernels of the other frames would use (76 registers, 47 KB here:
 // a road map renders 2.5 % faster with frames in flight this way, 6 % slower one at a time; round 3, same-box A/B).
+template <bool CULL>
 __global__ void __launch_bounds__(256) k_flatten_strokes(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
                                                         const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes, Control *control,
                                                         LineSoup *lines, uint32_t *heavy_list, uint32_t min_lines, uint32_t *arc_items,
                                                         uint32_t arc_shard_cap) {
     __shared__ FlattenShared<FLATTEN_STROKE_ROUND_LINES> sh;  // 30 KB of staging + 16 KB of arcs: three workgroups per CU
     __shared__ ArcQueue arcs;
-    stroke_workgroup(sh, arcs, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, min_lines, arc_items,
+    stroke_workgroup<CULL>(sh, arcs, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, min_lines, arc_items,
                      arc_shard_cap);
 }
 
-template <bool COOP>
+template <bool COOP, bool CULL>
 __global__ void __launch_bounds__(256, 2) k_flatten_heavy(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
                                                           const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
                                                           Control *control, LineSoup *lines, const uint32_t *__restrict__ heavy_list,
@@ -1615,7 +1722,7 @@ __global__ void __launch_bounds__(256, 2) k_flatten_heavy(Config cfg, uint32_t n
                                                           uint32_t arc_shard_cap) {
     __shared__ FlattenShared<FLATTEN_LDS_LINES> sh;
     __shared__ EulerCoopLds coop[COOP ? 4 : 1];
-    heavy_workgroups<HEAVY_FIRST | HEAVY_SET_ASIDE, COOP>(sh, coop, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list,
+    heavy_workgroups<HEAVY_FIRST | HEAVY_SET_ASIDE, COOP, CULL>(sh, coop, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list,
                                                     stroke_kernel_min_lines, arc_items, arc_shard_cap);
 }
 
@@ -1685,7 +1792,7 @@ __device__ __forceinline__ bool front_barrier(uint32_t *sync, uint32_t target, b
     return !tripped;
 }
 
-template <bool HEAVY>
+template <bool HEAVY, bool CULL>
 __global__ void __launch_bounds__(256) k_front(Config cfg, FrontArgs a) {
     const uint32_t tid = threadIdx.x, wg = blockIdx.x, n_wg = gridDim.x;
     uint32_t target = a.sync_base;
@@ -1716,7 +1823,7 @@ __global__ void __launch_bounds__(256) k_front(Config cfg, FrontArgs a) {
             if (b < a.n_draw_blocks)
                 draw_scan_workgroup(cfg, a.scene, a.control, a.draw_state, a.path_bboxes, a.draw_monoids, a.info_bin_data, a.clip_inp);
             else
-                flatten_light_workgroup(cfg, b - a.n_draw_blocks, a.n_tags, a.scene, a.tag_monoids, a.path_bboxes, a.control, a.lines, a.heavy_list);
+                flatten_light_workgroup<CULL>(cfg, b - a.n_draw_blocks, a.n_tags, a.scene, a.tag_monoids, a.path_bboxes, a.control, a.lines, a.heavy_list);
             __syncthreads();
         }
         FRONT_STAGE_END(FRONT_LIGHT);
@@ -1726,7 +1833,7 @@ __global__ void __launch_bounds__(256) k_front(Config cfg, FrontArgs a) {
             // (no stroke workgroups: every stroked line is the heavy list's; the workgroups stride over the list themselves)
             __shared__ __attribute__((aligned(16))) unsigned char smem[FLATTEN_MAIN_LDS];
             if (ok)
-            heavy_workgroups<HEAVY_FIRST, true>(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem),
+            heavy_workgroups<HEAVY_FIRST, true, CULL>(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem),
                                                 reinterpret_cast<EulerCoopLds *>(smem + FLATTEN_ARCS_AT), wg, n_wg, cfg, a.n_tags, a.scene, a.tag_monoids,
                                                 a.path_bboxes, a.control, a.lines, a.heavy_list, 0xffffffffu, a.arc_items, a.arc_shard_cap);
             FRONT_STAGE_END(FRONT_HEAVY);
@@ -1822,14 +1929,22 @@ uint32_t launch_front(const Frame &f, hipStream_t s, uint32_t stages, bool with_
         if (n_wg > FRONT_MAX_WG) n_wg = FRONT_MAX_WG;
     }
 #endif
-    if (stages & FRONT_HEAVY) hipLaunchKernelGGL(k_front<true>, dim3(n_wg), dim3(256), 0, s, f.cfg, a);
-    else hipLaunchKernelGGL(k_front<false>, dim3(n_wg), dim3(256), 0, s, f.cfg, a);
+    // (Frame::viewport_cull picks the instantiation: flush_staged_lines says why it is not a run-time flag)
+    if (f.viewport_cull) {
+        if (stages & FRONT_HEAVY) hipLaunchKernelGGL((k_front<true, true>), dim3(n_wg), dim3(256), 0, s, f.cfg, a);
+        else hipLaunchKernelGGL((k_front<false, true>), dim3(n_wg), dim3(256), 0, s, f.cfg, a);
+    } else {
+        if (stages & FRONT_HEAVY) hipLaunchKernelGGL((k_front<true, false>), dim3(n_wg), dim3(256), 0, s, f.cfg, a);
+        else hipLaunchKernelGGL((k_front<false, false>), dim3(n_wg), dim3(256), 0, s, f.cfg, a);
+    }
     uint32_t n_stages = 0u;
     for (uint32_t b = stages; b != 0u; b &= b - 1u) n_stages++;
     return n_wg == 1u ? 0u : n_wg * (n_stages - 1u);
 }
 
-void launch_flatten(const Frame &f, hipStream_t s, hipEvent_t *mid, bool with_draw_scan, bool light_done) {
+// (CULL = Frame::viewport_cull: the kernels' instantiations that leave lines off the target out of the soup)
+template <bool CULL>
+static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mid, bool with_draw_scan, bool light_done) {
     uint32_t n_tags = f.n_tag_words * 4u;
     uint32_t grid = (n_tags + FLATTEN_BLOCK_TAGS - 1u) / FLATTEN_BLOCK_TAGS;
     if (grid == 0) {
@@ -1843,7 +1958,7 @@ void launch_flatten(const Frame &f, hipStream_t s, hipEvent_t *mid, bool with_dr
     }
     const uint32_t grid_draw = with_draw_scan ? (f.cfg.layout.n_draw_objects + DRAW_PART - 1u) / DRAW_PART : 0u;
     if (!light_done)
-        hipLaunchKernelGGL(k_flatten_light, dim3(grid + grid_draw), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
+        hipLaunchKernelGGL(k_flatten_light<CULL>, dim3(grid + grid_draw), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                            f.lines, f.heavy_list, grid_draw, f.draw_state, f.draw_monoids, f.info_bin_data, f.clip_inp);
     if (mid) (void)hipEventRecord(mid[0], s);
     // enough workgroups for a wave per list entry on small scenes and for one round per workgroup on large ones
@@ -1865,10 +1980,10 @@ void launch_flatten(const Frame &f, hipStream_t s, hipEvent_t *mid, bool with_dr
     const uint32_t min_lines = f.launch_stroke_kernel ? f.stroke_kernel_min_lines : 0xffffffffu;  // (no stroke workgroups: every line is the heavy ones')
     if (f.flatten_side_by_side) {
         if (f.flatten_coop)
-            hipLaunchKernelGGL(k_flatten_main<true>, dim3(grid_heavy + grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
+            hipLaunchKernelGGL((k_flatten_main<true, CULL>), dim3(grid_heavy + grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
                                f.control, f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap, grid_heavy);
         else
-            hipLaunchKernelGGL(k_flatten_main<false>, dim3(grid_heavy + grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
+            hipLaunchKernelGGL((k_flatten_main<false, CULL>), dim3(grid_heavy + grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
                                f.control, f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap, grid_heavy);
         if (mid) (void)hipEventRecord(mid[1], s);
         // what the stroke workgroups set aside (arcs: a few per cent of the lines; handed-on lines: nearly none)
@@ -1876,21 +1991,26 @@ void launch_flatten(const Frame &f, hipStream_t s, hipEvent_t *mid, bool with_dr
             uint32_t grid_tail = (n_seg_max / 16u + 3u) / 4u;
             if (grid_tail > 1024u) grid_tail = 1024u;
             if (grid_tail < 4u) grid_tail = 4u;
-            hipLaunchKernelGGL(k_flatten_tail, dim3(grid_tail), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
+            hipLaunchKernelGGL(k_flatten_tail<CULL>, dim3(grid_tail), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                                f.lines, f.heavy_list, f.arc_items, arc_shard_cap);
         }
     } else {
         if (grid_strokes != 0u)
-            hipLaunchKernelGGL(k_flatten_strokes, dim3(grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
+            hipLaunchKernelGGL(k_flatten_strokes<CULL>, dim3(grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
                                f.control, f.lines, f.heavy_list, f.stroke_kernel_min_lines, f.arc_items, arc_shard_cap);
         if (mid) (void)hipEventRecord(mid[1], s);
         if (f.flatten_coop)
-            hipLaunchKernelGGL(k_flatten_heavy<true>, dim3(grid_heavy), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
+            hipLaunchKernelGGL((k_flatten_heavy<true, CULL>), dim3(grid_heavy), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                                f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap);
         else
-            hipLaunchKernelGGL(k_flatten_heavy<false>, dim3(grid_heavy), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
+            hipLaunchKernelGGL((k_flatten_heavy<false, CULL>), dim3(grid_heavy), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                                f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap);
     }
+}
+
+void launch_flatten(const Frame &f, hipStream_t s, hipEvent_t *mid, bool with_draw_scan, bool light_done) {
+    if (f.viewport_cull) launch_flatten_kernels<true>(f, s, mid, with_draw_scan, light_done);
+    else launch_flatten_kernels<false>(f, s, mid, with_draw_scan, light_done);
 }
 
 }  // namespace vk

@@ -35,8 +35,9 @@ class RenderParams:
 
 
 class RendererOptions:
-    def __init__(self, device=0, antialiasing_support=7, capacities=None):
+    def __init__(self, device=0, antialiasing_support=7, capacities=None, viewport_cull=False):
         self.device, self.antialiasing_support, self.capacities = device, antialiasing_support, capacities
+        self.viewport_cull = viewport_cull  # Engine.set_viewport_cull
 
 
 def _caps(capacities):
@@ -108,6 +109,10 @@ class Renderer:
         if not self._h:
             raise VelloHipError(err.value.decode() or "vello_hip_create failed")
         self._overrides = {}  # image id -> source (the renderer keeps it alive, as upstream holds the wgpu::Texture)
+        if getattr(options, "viewport_cull", False):
+            r = self._lib.vello_hip_set_viewport_cull(self._lib.vh_renderer_engine(self._h), 1)
+            if r != 0:
+                raise VelloHipError(f"vello_hip_set_viewport_cull failed ({r})")
 
     def __del__(self):
         try:
@@ -319,6 +324,12 @@ class Engine:
 
     def set_auto_grow(self, enabled=True):
         self._check(self._lib.vello_hip_set_auto_grow(self._h, 1 if enabled else 0), "set_auto_grow")
+
+    def set_viewport_cull(self, enabled=True):
+        """vello_hip_set_viewport_cull: flatten leaves the lines that lie wholly off the target's top, bottom or right side out
+        of the soup (bump["lines"] counts the rest); path boxes and everything behind the soup, the image included, are unchanged.
+        Applies to frames enqueued after the call."""
+        self._check(self._lib.vello_hip_set_viewport_cull(self._h, 1 if enabled else 0), "set_viewport_cull")
 
     def set_debug_flags(self, no_cull=False, stroke_kernel=False, seq_clip=False, fine_slices=False, flatten_coop=False, flatten_alone=False, no_fusion=False):
         """vello_hip_set_debug_flags: no_cull makes coarse emit every draw (reference-exact PTCL / segments); stroke_kernel
