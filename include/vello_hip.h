@@ -230,6 +230,10 @@ uint32_t vello_hip_last_render_attempts(vello_hip_ctx *ctx);
 /* Launches in which the stages of a small scene shared a kernel (VELLO_HIP_DEBUG_NO_FUSION), counted since the context was
  * created: lets a test see that the scene it renders took that path. */
 uint64_t vello_hip_fused_launches(vello_hip_ctx *ctx);
+/* Scene buffers allocated since the context was created (vello_hip_upload_scene's shared one and the private ones of
+ * vello_hip_render_frame's lanes): lets a test see that frames whose scenes fit the buffers they have allocate nothing -- a
+ * re-allocation frees device memory, which waits for every frame in flight. */
+uint64_t vello_hip_scene_allocations(vello_hip_ctx *ctx);
 int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                                   const vello_hip_render_params *params, vello_hip_capacities *out);
 
@@ -255,6 +259,41 @@ int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_len, const 
  * lies off the target (a zoomed or panned view); on a scene that is all on the target flatten pays the test for nothing.
  * VELLO_HIP_E_INVALID for a null context. */
 int vello_hip_set_viewport_cull(vello_hip_ctx *ctx, int enabled);
+
+/* View transform for the frames that follow (default: none).  `view` is a vello_encoding::Transform, [m0 m1 m2 m3 t0 t1]: the
+ * matrix [[m0 m2] [m1 m3]] and the translation (t0, t1).  A frame enqueued while a view V is set is rendered as if every entry T of
+ * the scene's transform stream -- the words [transform_base, style_base) of the packed scene, n_xf = (style_base - transform_base) / 6
+ * entries -- had been replaced by V.T, which is what Scene::append(scene, Some(V)) does to a scene on the host, without encoding,
+ * packing or uploading anything.  V.T is computed as Transform::mul computes it (vello_encoding/src/math.rs:51-73): in f32, every
+ * product and every sum rounded on its own, in this operand order and association:
+ *     m0' = V.m0*T.m0 + V.m2*T.m1        m1' = V.m1*T.m0 + V.m3*T.m1
+ *     m2' = V.m0*T.m2 + V.m2*T.m3        m3' = V.m1*T.m2 + V.m3*T.m3
+ *     t0' = (V.m0*T.t0 + V.m2*T.t1) + V.t0
+ *     t1' = (V.m1*T.t0 + V.m3*T.t1) + V.t1
+ *   1. No other word of the scene changes.  A path encoded before any transform (trans_ix = 0 - 1: the zero-width stroke clip a
+ *      scene may begin with, scene.rs:179-183) reads the six words BELOW the stream; it keeps reading exactly those words,
+ *      uncomposed -- as it would after a host-side replacement of the stream.
+ *   2. The resident scene is never modified: vello_hip_read_buffer(VELLO_HIP_BUF_SCENE) returns the uploaded bytes whatever views
+ *      have been rendered, and VELLO_HIP_BUF_CONFIG holds the scene's own layout.  NULL restores frames without a view bit for
+ *      bit, in every buffer and counter.
+ *   3. A non-null view always composes, the identity included (on a scene of finite transforms the result equals the off state).
+ *   4. VELLO_HIP_E_INVALID, and nothing changes, for a null context or a view with a NaN or infinite entry.  Singular and
+ *      mirroring views are legal: what they show is what the composed scene shows.
+ *   5. Applies to frames enqueued after the call on every entry point that renders (render, render_frame, render_resident, and
+ *      run_stages when the range holds FLATTEN or DRAW_SCAN) and on all in-flight buffer sets; frames already enqueued keep the
+ *      view they were enqueued with: four frames in flight may show four views of one resident scene.
+ *   6. Composes with vello_hip_set_viewport_cull: the rule is applied to the lines of the viewed scene.
+ *   7. With vello_hip_set_auto_grow the blocking vello_hip_render sizes the pools with vello_hip_estimate_capacities_view and the
+ *      context's view.
+ * The composed words are written by one small kernel (k_view_transforms, a lane per entry) at the head of every frame that has a
+ * view, into a per-frame copy behind the scene's bytes; nothing crosses PCIe.  Scenes whose packed bytes and copies together
+ * exceed 2^32 words are refused with VELLO_HIP_E_INVALID when a frame with a view is enqueued. */
+int vello_hip_set_view_transform(vello_hip_ctx *ctx, const float view[6] /* nullable: off (default) */);
+/* vello_hip_estimate_capacities with V composed, by the same formula, into every transform the estimator reads; equal to it for
+ * view == NULL.  VELLO_HIP_E_INVALID for a view with a NaN or infinite entry. */
+int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                                       const vello_hip_render_params *params, const float view[6] /* nullable */,
+                                       vello_hip_capacities *out);
 
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a
  * later opaque full-tile cover is normally not emitted; the image is the same, but bump.segments / bump.ptcl and the

@@ -110,6 +110,9 @@ unsafe extern "C" {
     pub fn vello_hip_estimate_capacities(scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, params: *const vello_hip_render_params, out: *mut vello_hip_capacities) -> c_int;
     pub fn vello_hip_set_auto_grow(ctx: *mut vello_hip_ctx, enabled: c_int) -> c_int;
     pub fn vello_hip_set_viewport_cull(ctx: *mut vello_hip_ctx, enabled: c_int) -> c_int;
+    pub fn vello_hip_scene_allocations(ctx: *mut vello_hip_ctx) -> u64;
+    pub fn vello_hip_set_view_transform(ctx: *mut vello_hip_ctx, view: *const f32) -> c_int;
+    pub fn vello_hip_estimate_capacities_view(scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, params: *const vello_hip_render_params, view: *const f32, out: *mut vello_hip_capacities) -> c_int;
     pub fn vello_hip_set_debug_flags(ctx: *mut vello_hip_ctx, flags: u32) -> c_int;
     pub fn vello_hip_set_frames_in_flight(ctx: *mut vello_hip_ctx, n: u32) -> c_int;
     pub fn vello_hip_sync_frame(ctx: *mut vello_hip_ctx, age: u32) -> c_int;

@@ -13,7 +13,8 @@ use ffi::*;
 use std::collections::HashMap;
 use vello::{AaConfig, AaSupport, RenderParams, Scene};
 use vello::peniko::ImageData;
-use vello_encoding::{Layout, Resolver};
+use vello::kurbo::Affine;
+use vello_encoding::{Layout, Resolver, Transform};
 
 #[derive(Debug)]
 pub enum Error {
@@ -90,6 +91,22 @@ impl HipRenderer {
     /// frames rendered after the call.
     pub fn set_viewport_cull(&mut self, enabled: bool) {
         unsafe { vello_hip_set_viewport_cull(self.ctx, enabled as c_int) };
+    }
+
+    /// `vello_hip_set_view_transform`: the frames rendered after the call show the scene as `Scene::append(scene, Some(view))`
+    /// would have encoded it -- the engine composes `view` in front of every transform of the packed scene on the GPU, in f32 as
+    /// `Transform::mul` does (`include/vello_hip.h` has the contract).  `None` switches it off.  A view with a NaN or infinite
+    /// coefficient is refused and changes nothing.
+    pub fn set_view_transform(&mut self, view: Option<Affine>) -> Result<(), Error> {
+        let rc = match view {
+            Some(affine) => {
+                let t = Transform::from_kurbo(&affine);
+                let v: [f32; 6] = [t.matrix[0], t.matrix[1], t.matrix[2], t.matrix[3], t.translation[0], t.translation[1]];
+                unsafe { vello_hip_set_view_transform(self.ctx, v.as_ptr()) }
+            }
+            None => unsafe { vello_hip_set_view_transform(self.ctx, core::ptr::null()) },
+        };
+        if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
     }
 
     /// `Renderer::override_image` (vello/src/lib.rs:536-545): whenever the resolver schedules `image` for upload, its texels

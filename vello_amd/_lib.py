@@ -94,10 +94,14 @@ def load_library():
     sig("vello_hip_grow_pools", i32, [vp, c.POINTER(Bump), c.POINTER(Capacities)])
     sig("vello_hip_set_auto_grow", i32, [vp, i32])
     sig("vello_hip_set_viewport_cull", i32, [vp, i32])
+    sig("vello_hip_set_view_transform", i32, [vp, c.POINTER(c.c_float)])
     sig("vello_hip_set_debug_flags", i32, [vp, u32])
     sig("vello_hip_last_render_attempts", u32, [vp])
     sig("vello_hip_fused_launches", ctypes.c_uint64, [vp])
+    sig("vello_hip_scene_allocations", ctypes.c_uint64, [vp])
     sig("vello_hip_estimate_capacities", i32, [vp, sz, c.POINTER(LayoutStruct), c.POINTER(RenderParamsStruct), c.POINTER(Capacities)])
+    sig("vello_hip_estimate_capacities_view", i32, [vp, sz, c.POINTER(LayoutStruct), c.POINTER(RenderParamsStruct), c.POINTER(c.c_float),
+                                               c.POINTER(Capacities)])
     sig("vello_hip_gather_frames", i32, [c.POINTER(vp), u32, i32, c.POINTER(vp), c.POINTER(vp), sz])
     sig("vello_hip_gather_wait", i32, [c.POINTER(vp), u32])
     sig("vello_hip_sync_frame", i32, [vp, u32])
@@ -168,6 +172,7 @@ def load_library():
     sig("vh_renderer_free", None, [vp])
     sig("vh_renderer_render_to_texture", i32, [vp, vp, vp, sz, i32, u32, u32, fp, u32])
     sig("vh_renderer_render_to_texture_on", i32, [vp, vp, vp, sz, i32, u32, u32, fp, u32, vp])
+    sig("vh_renderer_render_to_texture_view", i32, [vp, vp, vp, sz, i32, u32, u32, fp, u32, vp, fp])
     sig("vh_renderer_override_image", i32, [vp, c.c_uint64, i32, c.c_uint64, c.c_uint64, c.POINTER(c.c_uint64)])
     sig("vh_renderer_mark_override_image_dirty", None, [vp, c.c_uint64])
     sig("vh_renderer_error", c.c_char_p, [vp])

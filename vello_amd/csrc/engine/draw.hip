@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(64) k_clip(Config cfg, const Clip *__restrict_
 void launch_draw_scan(const Frame &f, hipStream_t s) {
     uint32_t n_parts = (f.cfg.layout.n_draw_objects + DRAW_PART - 1u) / DRAW_PART;
     if (n_parts == 0) return;
-    hipLaunchKernelGGL(k_draw_scan, dim3(n_parts), dim3(256), 0, s, f.cfg, f.scene, f.control, f.draw_state, f.path_bboxes,
+    hipLaunchKernelGGL(k_draw_scan, dim3(n_parts), dim3(256), 0, s, xf_config(f), f.scene, f.control, f.draw_state, f.path_bboxes,
                        f.draw_monoids, f.info_bin_data, f.clip_inp);
 }
 

@@ -141,6 +141,16 @@ struct Frame {
     uint32_t aa;
     // device pointers
     const uint32_t *scene;
+    // The transform words flatten and draw_leaf read: entry ix lies at scene[(u32)(xf_base + ix * 6)] (read_transform, common.h).
+    // Without a view that is the scene's own stream (xf_base == cfg.layout.transform_base); with one (vello_hip_set_view_transform)
+    // it is the lane's composed copy, which k_view_transforms fills at the head of the frame -- slot -1 holds the six words below the
+    // stream verbatim, slots 0 .. n_xf-1 hold V.T.  The copy lives behind the scene's bytes in the scene's own allocation, so that it
+    // is reached with the same pointer and a u32 word offset: the kernels that read transforms are handed a Config whose
+    // layout.transform_base is xf_base (xf_config) and are the same code whether a view is set or not.  The pathtag scan keeps the
+    // scene's own Config: it judges indices against the scene's layout.
+    uint32_t xf_base;
+    bool has_view;
+    Xform view;
     Control *control;
     uint32_t *heavy_list;   // flatten: tag indices that need the Euler-spiral / stroker path
     uint32_t *arc_items;    // flatten: 16 words per round join / cap arc that a stroke workgroup leaves to the heavy code
@@ -191,6 +201,15 @@ struct Frame {
     uint32_t *front_sync;    // k_front's grid-barrier counter (per lane; only ever grows)
     Bump *bump() const { return &control->bump; }
 };
+
+// the Config of the kernels that read transforms (flatten's, the draw stage's): the frame's, with the transform words' base
+inline Config xf_config(const Frame &f) {
+    Config c = f.cfg;
+    c.layout.transform_base = f.xf_base;
+    return c;
+}
+// k_view_transforms (engine.hip): fills the frame's composed transform words; launched at the head of a frame that has a view
+void launch_view_transforms(const Frame &f, hipStream_t s);
 
 void launch_pathtag_scan(const Frame &f, hipStream_t s);
 // (mid: when not null, an event is recorded behind every kernel of the stage but the last: per-KERNEL times of a stage of

@@ -60,6 +60,44 @@ void launch_atlas_copy(const AtlasCopyDesc *descs, uint32_t n, uint64_t total, u
     hipLaunchKernelGGL(k_atlas_copy, dim3((uint32_t)wgs), dim3(256), 0, s, descs, n, total, (uint32_t)steps, atlas, atlas_w);
 }
 
+// k_view_transforms: the view transform of vello_hip_set_view_transform composed into a frame's own copy of the transform stream, a
+// lane per entry.  Slot i of `out` is entry i - 1: slot 0 is the six words BELOW the stream, copied verbatim (a path encoded before any
+// transform reads them, read_transform in common.h; zeros when the scene has no six words there -- the pathtag scan then hands out no
+// index -1), slots 1 .. n_xf are V.T as vello_encoding's Transform::mul computes it (math.rs:51-73): f32, every product and every sum
+// rounded on its own (the tree is built without fp contraction), in this operand order and association.  Six dword loads and six
+// dword stores per lane at a stride of 24 bytes: the stream is 4-byte aligned only, and a wave's 64 entries are 1.5 KB of
+// consecutive memory either way.  The kernel reads the scene and writes the copy; nothing else of the frame runs beside it on
+// the lane's stream.
+__global__ void __launch_bounds__(256) k_view_transforms(const uint32_t *__restrict__ scene, uint32_t transform_base, uint32_t n_xf, Xform v,
+                                                         uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i > n_xf) return;
+    uint32_t *o = out + (size_t)i * 6u;
+    if (i == 0u) {
+        const bool below = transform_base >= 6u;
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) o[k] = below ? scene[transform_base - 6u + k] : 0u;
+        return;
+    }
+    const Xform t = read_transform(scene, transform_base, i - 1u);
+    const float m0 = v.m0 * t.m0 + v.m2 * t.m1, m1 = v.m1 * t.m0 + v.m3 * t.m1;
+    const float m2 = v.m0 * t.m2 + v.m2 * t.m3, m3 = v.m1 * t.m2 + v.m3 * t.m3;
+    const float t0 = (v.m0 * t.t0 + v.m2 * t.t1) + v.t0, t1 = (v.m1 * t.t0 + v.m3 * t.t1) + v.t1;
+    o[0] = __float_as_uint(m0);
+    o[1] = __float_as_uint(m1);
+    o[2] = __float_as_uint(m2);
+    o[3] = __float_as_uint(m3);
+    o[4] = __float_as_uint(t0);
+    o[5] = __float_as_uint(t1);
+}
+
+void launch_view_transforms(const Frame &f, hipStream_t s) {
+    const uint32_t n_xf = (f.cfg.layout.style_base - f.cfg.layout.transform_base) / 6u;
+    // (slot 0 of the copy is entry -1: six words in front of xf_base)
+    hipLaunchKernelGGL(k_view_transforms, dim3((n_xf + 1u + 255u) / 256u), dim3(256), 0, s, f.scene, f.cfg.layout.transform_base, n_xf, f.view,
+                       const_cast<uint32_t *>(f.scene) + (f.xf_base - 6u));
+}
+
 }  // namespace vk
 
 namespace {
@@ -101,7 +139,15 @@ struct SceneSlot {
     // markers of open subpaths), stroked lines (-1: not known yet): picks the kernels that take the list (Frame::flatten_coop)
     int64_t heavy_curves = -1, heavy_strokes = -1;
     uint64_t generation = 0;  // bumped by every upload into the slot: a lane's finished frame speaks for the scene it rendered only
+    // The composed transform words of frames with a view (vello_hip_set_view_transform, Frame::xf_base): `view_sets` copies of
+    // (n_xf + 1) * 6 words each, from word `view_at` of the scene's allocation -- behind the scene's bytes and their slack, never
+    // part of what VELLO_HIP_BUF_SCENE shows.  The shared slot holds a copy per lane (frames in flight have views of their own), a
+    // lane's private slot one.
+    size_t view_at = 0;
+    size_t view_cap_bytes = 0;  // bytes allocated from view_at on (ensure_scene)
+    uint32_t view_sets = 0, view_set_words = 0;
 };
+constexpr uint32_t MAX_LANES = 8;
 
 struct Lane {
     hipStream_t stream = nullptr;
@@ -156,6 +202,8 @@ struct vello_hip_ctx {
     uint32_t next_lane = 0, last_lane = 0;
     bool auto_grow = false;
     bool viewport_cull = false;  // vello_hip_set_viewport_cull: copied into every Frame when it is prepared
+    bool has_view = false;       // vello_hip_set_view_transform: likewise
+    Xform view{1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
     hipStream_t copy_stream = nullptr;  // vello_hip_gather_frames: this context's peer copy
     hipEvent_t frame_done = nullptr;
     // vello_hip_write_image: atlas uploads are stream-ordered, not host-synchronous (wgpu's queue.write_texture is queued
@@ -170,6 +218,7 @@ struct vello_hip_ctx {
     bool force_brushes = false;  // pre-warm: run fine's brush specialisation on a scene without brushes
     uint32_t last_render_attempts = 0;  // rounds the last vello_hip_render needed (robust mode)
     uint64_t fused_launches = 0;  // k_front launches so far (vello_hip_fused_launches)
+    uint64_t scene_allocations = 0;  // scene buffers allocated so far (vello_hip_scene_allocations)
     // last frame
     Config cfg{};
     bool have_cfg = false;
@@ -404,6 +453,20 @@ int configure(vello_hip_ctx *c, const SceneSlot &sc, const vello_hip_render_para
     return 0;
 }
 
+// Where entry 0 of lane l's copy of the transform words lies, in words from the scene's start (SceneSlot::view_at; six words into
+// the copy: slot -1 comes first).  VELLO_HIP_E_INVALID for a scene so large that the copy is out of a u32 offset's reach.  The entry
+// points that rotate the lanes ask before they rotate, so that a refused frame leaves the rotation where it was.
+int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base) {
+    const size_t set = l.use_own ? 0u : (size_t)(&l - c->lanes.data());
+    const uint64_t at = (uint64_t)sc.view_at + (uint64_t)set * sc.view_set_words + 6u;
+    if (set >= sc.view_sets || at + sc.view_set_words > 0xffffffffull) {
+        c->last_error = "the scene is too large for a view transform (its transform words must lie within 2^32 words of its start)";
+        return VELLO_HIP_E_INVALID;
+    }
+    base = (uint32_t)at;
+    return 0;
+}
+
 int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, void *out_device, size_t out_stride, Frame &f,
                   bool upload_cfg) {
     const SceneSlot &sc = slot_of(c, l);
@@ -458,6 +521,10 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
     f.n_scene_words = (uint32_t)(sc.scene_len / 4u);
     f.aa = p->aa;
     f.scene = (const uint32_t *)sc.scene.ptr;
+    f.has_view = c->has_view;
+    f.view = c->view;
+    f.xf_base = sc.layout.transform_base;
+    if (f.has_view && (r = view_base(c, sc, l, f.xf_base))) return r;
     f.control = (Control *)l.zero_region.ptr;
     f.zero_bytes = (uint32_t)sc.zero_bytes;
     f.front_sync = (uint32_t *)l.front_sync.ptr;
@@ -602,6 +669,11 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
         // (the heavy list aboard: the kernels of the cooperative walk, no stroke workgroups -- not when a debug flag asks for others)
         fuse_all = fuse_a && fuse_b && (pm & (1u << VELLO_HIP_STAGE_CLIP)) == 0u && f.cfg.layout.n_clips == 0u &&
                    flatten_n_seg_max(f) <= FRONT_TINY_SEGMENTS && f.flatten_coop && f.stroke_kernel_min_lines != 0u;
+    }
+    // a frame with a view: its transform words first (outside every stage's events), when the range holds a stage that reads them
+    if (f.has_view && first <= VELLO_HIP_STAGE_DRAW_SCAN && last >= VELLO_HIP_STAGE_FLATTEN) {
+        launch_view_transforms(f, st);
+        HIP_TRY(c, hipGetLastError());
     }
     for (int s = first; s <= last; s++) {
         bool prof = ((c->prof_mask >> s) & 1u) != 0u;
@@ -901,7 +973,7 @@ void vello_hip_destroy(vello_hip_ctx *c) {
 }
 
 int vello_hip_set_frames_in_flight(vello_hip_ctx *c, uint32_t n) {
-    if (!c || n < 1 || n > 8) return VELLO_HIP_E_INVALID;
+    if (!c || n < 1 || n > MAX_LANES) return VELLO_HIP_E_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     int r = sync_all(c);
     if (r) return r;
@@ -926,6 +998,27 @@ int vello_hip_set_frames_in_flight(vello_hip_ctx *c, uint32_t n) {
     return VELLO_HIP_OK;
 }
 
+// ensure() for a slot's scene buffer: `bytes` of scene (what VELLO_HIP_BUF_SCENE shows) and, from the next 16-byte boundary on, a
+// tail of `tail` bytes for the composed transform words.  Like ensure() it never shrinks -- neither part: the tail's capacity is
+// kept in a field of its own, written only where the allocation happens, so that scenes whose transform counts go up and down
+// (a lane's vello_hip_render_frame scenes) settle on the largest and allocate nothing from then on.
+static int ensure_scene(vello_hip_ctx *c, SceneSlot &sc, size_t bytes, size_t tail) {
+    if (sc.scene.ptr && sc.scene.size >= bytes && sc.view_cap_bytes >= tail) return 0;
+    const size_t visible = sc.scene.size > bytes ? sc.scene.size : bytes;
+    const size_t cap = sc.view_cap_bytes > tail ? sc.view_cap_bytes : tail;
+    if (sc.scene.ptr) HIP_TRY(c, hipFree(sc.scene.ptr));
+    sc.scene.ptr = nullptr;
+    sc.scene.size = 0;
+    sc.view_cap_bytes = 0;
+    const size_t at = (visible + 15u) & ~(size_t)15u;
+    HIP_TRY(c, hipMalloc(&sc.scene.ptr, at + cap + 256));
+    sc.scene.size = visible;
+    sc.view_at = at / 4u;
+    sc.view_cap_bytes = cap;
+    c->scene_allocations++;
+    return 0;
+}
+
 // Validates the layout, sizes the slot and copies scene + ramps on `st`; returns once the source buffers may be
 // reused (they are caller-owned only for the duration of the call, recording.rs:124-129).
 static int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *scene, size_t scene_len,
@@ -945,7 +1038,12 @@ static int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint
     }
     int r;
     // 64 B of slack: flatten reads tag ix+1 and the (wrapped) style word of pre-style tags speculatively
-    if ((r = ensure(c, sc.scene, scene_len + 64))) return r;
+    // ... and, behind them, room for the composed transform words of frames with a view (SceneSlot::view_at)
+    const uint32_t set_words = ((L.style_base - L.transform_base) / 6u + 1u) * 6u;
+    const uint32_t sets = &sc == &c->shared ? MAX_LANES : 1u;
+    if ((r = ensure_scene(c, sc, scene_len + 64, (size_t)set_words * sets * 4u))) return r;
+    sc.view_sets = sets;
+    sc.view_set_words = set_words;
     sc.layout = L;
     sc.scene_len = scene_len;
     uint32_t n_path_tags = (L.path_data_base - L.path_tag_base) * 4u;
@@ -1027,6 +1125,8 @@ int vello_hip_render_frame(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
     if (r) return r;
     l.use_own = true;
     if ((r = alloc_lane_scene(c, l, l.own))) return r;
+    uint32_t xf_base;
+    if (c->has_view && (r = view_base(c, l.own, l, xf_base))) return r;
     c->next_lane = (li + 1u) % c->n_active;
     c->last_lane = li;
     Frame f;
@@ -1200,6 +1300,8 @@ int vello_hip_render_resident(vello_hip_ctx *c, const vello_hip_render_params *p
         l.use_own = false;
         if ((r = alloc_lane_scene(c, l, c->shared))) return r;
     }
+    uint32_t xf_base;
+    if (c->has_view && c->shared.resident && (r = view_base(c, c->shared, l, xf_base))) return r;
     c->next_lane = (li + 1u) % c->n_active;
     c->last_lane = li;
     Frame f;
@@ -1310,6 +1412,7 @@ int vello_hip_sync(vello_hip_ctx *c) {
 
 uint32_t vello_hip_last_render_attempts(vello_hip_ctx *c) { return c ? c->last_render_attempts : 0u; }
 uint64_t vello_hip_fused_launches(vello_hip_ctx *c) { return c ? c->fused_launches : 0u; }
+uint64_t vello_hip_scene_allocations(vello_hip_ctx *c) { return c ? c->scene_allocations : 0u; }
 
 void *vello_hip_get_stream(vello_hip_ctx *c) { return c ? (void *)c->lanes[c->last_lane].stream : nullptr; }
 
@@ -1428,6 +1531,25 @@ int vello_hip_set_viewport_cull(vello_hip_ctx *c, int enabled) {
     return VELLO_HIP_OK;
 }
 
+// As the culling switch: a frame takes the view when it is prepared (Frame::view travels to k_view_transforms by value, and the
+// frame's composed transform words are its lane's own), so frames already enqueued keep theirs.  What the engine remembers of a
+// scene's earlier frames (SceneSlot) only picks among kernels and launch shapes that are all correct for any view: DESIGN.md 13.
+int vello_hip_set_view_transform(vello_hip_ctx *c, const float view[6]) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    if (!view) {
+        c->has_view = false;
+        return VELLO_HIP_OK;
+    }
+    for (int k = 0; k < 6; k++)
+        if (!(view[k] - view[k] == 0.0f)) {  // NaN or infinity
+            c->last_error = "set_view_transform: the view has an entry that is not finite";
+            return VELLO_HIP_E_INVALID;
+        }
+    c->has_view = true;
+    c->view = Xform{view[0], view[1], view[2], view[3], view[4], view[5]};
+    return VELLO_HIP_OK;
+}
+
 // Robust mode, before the first attempt: when the scene is large against the current pools, size them from
 // vello_hip_estimate_capacities (estimate.rs's counting rules on the packed scene) instead of finding the demand by
 // overflowing stage after stage.  The cheap test first: every path segment yields at least one line.
@@ -1440,11 +1562,13 @@ static int presize_pools(vello_hip_ctx *c, const uint8_t *scene, size_t scene_le
     uint64_t n_seg = 0;
     for (size_t i = 0; i < n_tags; i++) n_seg += (tags[i] & 3u) != 0u;
     const uint64_t n_tiles = (uint64_t)((params->width + 15u) / 16u) * ((params->height + 15u) / 16u);
-    if (4u * n_seg <= c->caps.lines && 8u * n_seg <= c->caps.seg_counts && 4u * n_seg + 8u * layout->n_paths <= c->caps.tiles &&
+    // (the cheap test stands for content at the scale it was encoded at: under a view the estimator is always asked)
+    if (!c->has_view && 4u * n_seg <= c->caps.lines && 8u * n_seg <= c->caps.seg_counts && 4u * n_seg + 8u * layout->n_paths <= c->caps.tiles &&
         160u * n_tiles + 16u * n_seg <= c->caps.ptcl)
         return VELLO_HIP_OK;
     vello_hip_capacities est;
-    if (vello_hip_estimate_capacities(scene, scene_len, layout, params, &est) != VELLO_HIP_OK) return VELLO_HIP_OK;
+    const float view[6] = {c->view.m0, c->view.m1, c->view.m2, c->view.m3, c->view.t0, c->view.t1};
+    if (vello_hip_estimate_capacities_view(scene, scene_len, layout, params, c->has_view ? view : nullptr, &est) != VELLO_HIP_OK) return VELLO_HIP_OK;
     vello_hip_capacities d = c->caps;
     bool grew = false;
     auto want = [&](uint32_t &cap, uint32_t need) {

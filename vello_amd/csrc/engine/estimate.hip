@@ -91,9 +91,13 @@ struct PathAcc {
 
 }  // namespace
 
-extern "C" int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
-                                             const vello_hip_render_params *params, vello_hip_capacities *out) {
+// `view` (nullable): vello_hip_set_view_transform's V, composed with every entry of the transform stream where it is read
+extern "C" int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                                                  const vello_hip_render_params *params, const float view[6], vello_hip_capacities *out) {
     if ((!scene && scene_len) || !layout || !params || !out || (scene_len & 3u)) return VELLO_HIP_E_INVALID;
+    if (view)
+        for (int k = 0; k < 6; k++)
+            if (!(view[k] - view[k] == 0.0f)) return VELLO_HIP_E_INVALID;  // NaN or infinity, as vello_hip_set_view_transform
     const vello_hip_layout &L = *layout;
     const size_t words = scene_len / 4u;
     if (L.path_tag_base > L.path_data_base || L.path_data_base > L.draw_tag_base || L.draw_tag_base > L.draw_data_base ||
@@ -248,11 +252,17 @@ extern "C" int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_
         }
         if (t & vk::PATH_TAG_TRANSFORM) {
             if (n_xf_seen < n_xf) {
-                for (int k = 0; k < 6; k++) {
-                    float f;
-                    std::memcpy(&f, &w[L.transform_base + n_xf_seen * 6u + k], 4);
-                    xf.m[k] = f;
+                float t[6];
+                std::memcpy(t, &w[L.transform_base + n_xf_seen * 6u], sizeof t);
+                if (view) {
+                    // V.T in f32, as k_view_transforms (engine.hip) and Transform::mul (math.rs:51-73) compute it: the estimator sees
+                    // the transform words the frame's kernels read
+                    const float *v = view;
+                    const float c[6] = {v[0] * t[0] + v[2] * t[1], v[1] * t[0] + v[3] * t[1], v[0] * t[2] + v[2] * t[3], v[1] * t[2] + v[3] * t[3],
+                                        (v[0] * t[4] + v[2] * t[5]) + v[4], (v[1] * t[4] + v[3] * t[5]) + v[5]};
+                    std::memcpy(t, c, sizeof t);
                 }
+                for (int k = 0; k < 6; k++) xf.m[k] = t[k];
             }
             n_xf_seen++;
         }
@@ -288,4 +298,9 @@ extern "C" int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_
     out->ptcl = cap32(128u * n_tiles + 2u * n_segments + 7u * T.ptcl_pairs + 4096u);
     out->blend_spill = 0u;  // clip depth is not visible in the path streams: left to the caller / auto-grow
     return VELLO_HIP_OK;
+}
+
+extern "C" int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                                             const vello_hip_render_params *params, vello_hip_capacities *out) {
+    return vello_hip_estimate_capacities_view(scene, scene_len, layout, params, nullptr, out);
 }

@@ -1930,22 +1930,42 @@ uint32_t launch_front(const Frame &f, hipStream_t s, uint32_t stages, bool with_
     }
 #endif
     // (Frame::viewport_cull picks the instantiation: flush_staged_lines says why it is not a run-time flag)
-    if (f.viewport_cull) {
-        if (stages & FRONT_HEAVY) hipLaunchKernelGGL((k_front<true, true>), dim3(n_wg), dim3(256), 0, s, f.cfg, a);
-        else hipLaunchKernelGGL((k_front<false, true>), dim3(n_wg), dim3(256), 0, s, f.cfg, a);
-    } else {
-        if (stages & FRONT_HEAVY) hipLaunchKernelGGL((k_front<true, false>), dim3(n_wg), dim3(256), 0, s, f.cfg, a);
-        else hipLaunchKernelGGL((k_front<false, false>), dim3(n_wg), dim3(256), 0, s, f.cfg, a);
+    auto launch = [&](const Config &cfg, const FrontArgs &args) {
+        const bool heavy = (args.stages & FRONT_HEAVY) != 0u;
+        if (f.viewport_cull) {
+            if (heavy) hipLaunchKernelGGL((k_front<true, true>), dim3(n_wg), dim3(256), 0, s, cfg, args);
+            else hipLaunchKernelGGL((k_front<false, true>), dim3(n_wg), dim3(256), 0, s, cfg, args);
+        } else {
+            if (heavy) hipLaunchKernelGGL((k_front<true, false>), dim3(n_wg), dim3(256), 0, s, cfg, args);
+            else hipLaunchKernelGGL((k_front<false, false>), dim3(n_wg), dim3(256), 0, s, cfg, args);
+        }
+    };
+    auto barriers = [&](uint32_t st) {  // what a launch of these stages adds to the counter
+        uint32_t n = 0u;
+        for (uint32_t b = st; b != 0u; b &= b - 1u) n++;
+        return n_wg == 1u ? 0u : n_wg * (n - 1u);
+    };
+    // A frame with a view (Frame::has_view): the pathtag scan judges the tag stream against the scene's own layout, the stages
+    // behind it read the composed transform words through theirs (xf_config) -- two launches of the same kernel, cut behind the scan
+    const uint32_t scan_part = FRONT_ZERO | FRONT_PATHTAG;
+    if (f.has_view && (stages & FRONT_PATHTAG) != 0u && (stages & ~scan_part) != 0u) {
+        FrontArgs a0 = a, a1 = a;
+        a0.stages = stages & scan_part;
+        a1.stages = stages & ~scan_part;
+        a1.sync_base = sync_base + barriers(a0.stages);
+        launch(f.cfg, a0);
+        launch(xf_config(f), a1);
+        return barriers(a0.stages) + barriers(a1.stages);
     }
-    uint32_t n_stages = 0u;
-    for (uint32_t b = stages; b != 0u; b &= b - 1u) n_stages++;
-    return n_wg == 1u ? 0u : n_wg * (n_stages - 1u);
+    launch((stages & FRONT_PATHTAG) != 0u ? f.cfg : xf_config(f), a);
+    return barriers(stages);
 }
 
 // (CULL = Frame::viewport_cull: the kernels' instantiations that leave lines off the target out of the soup)
 template <bool CULL>
 static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mid, bool with_draw_scan, bool light_done) {
     uint32_t n_tags = f.n_tag_words * 4u;
+    const Config cx = xf_config(f);  // (the transform words: the scene's stream, or the view's composed copy)
     uint32_t grid = (n_tags + FLATTEN_BLOCK_TAGS - 1u) / FLATTEN_BLOCK_TAGS;
     if (grid == 0) {
         if (with_draw_scan && !light_done) launch_draw_scan(f, s);
@@ -1958,7 +1978,7 @@ static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mi
     }
     const uint32_t grid_draw = with_draw_scan ? (f.cfg.layout.n_draw_objects + DRAW_PART - 1u) / DRAW_PART : 0u;
     if (!light_done)
-        hipLaunchKernelGGL(k_flatten_light<CULL>, dim3(grid + grid_draw), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
+        hipLaunchKernelGGL(k_flatten_light<CULL>, dim3(grid + grid_draw), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                            f.lines, f.heavy_list, grid_draw, f.draw_state, f.draw_monoids, f.info_bin_data, f.clip_inp);
     if (mid) (void)hipEventRecord(mid[0], s);
     // enough workgroups for a wave per list entry on small scenes and for one round per workgroup on large ones
@@ -1980,10 +2000,10 @@ static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mi
     const uint32_t min_lines = f.launch_stroke_kernel ? f.stroke_kernel_min_lines : 0xffffffffu;  // (no stroke workgroups: every line is the heavy ones')
     if (f.flatten_side_by_side) {
         if (f.flatten_coop)
-            hipLaunchKernelGGL((k_flatten_main<true, CULL>), dim3(grid_heavy + grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
+            hipLaunchKernelGGL((k_flatten_main<true, CULL>), dim3(grid_heavy + grid_strokes), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
                                f.control, f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap, grid_heavy);
         else
-            hipLaunchKernelGGL((k_flatten_main<false, CULL>), dim3(grid_heavy + grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
+            hipLaunchKernelGGL((k_flatten_main<false, CULL>), dim3(grid_heavy + grid_strokes), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
                                f.control, f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap, grid_heavy);
         if (mid) (void)hipEventRecord(mid[1], s);
         // what the stroke workgroups set aside (arcs: a few per cent of the lines; handed-on lines: nearly none)
@@ -1991,19 +2011,19 @@ static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mi
             uint32_t grid_tail = (n_seg_max / 16u + 3u) / 4u;
             if (grid_tail > 1024u) grid_tail = 1024u;
             if (grid_tail < 4u) grid_tail = 4u;
-            hipLaunchKernelGGL(k_flatten_tail<CULL>, dim3(grid_tail), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
+            hipLaunchKernelGGL(k_flatten_tail<CULL>, dim3(grid_tail), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                                f.lines, f.heavy_list, f.arc_items, arc_shard_cap);
         }
     } else {
         if (grid_strokes != 0u)
-            hipLaunchKernelGGL(k_flatten_strokes<CULL>, dim3(grid_strokes), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
+            hipLaunchKernelGGL(k_flatten_strokes<CULL>, dim3(grid_strokes), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
                                f.control, f.lines, f.heavy_list, f.stroke_kernel_min_lines, f.arc_items, arc_shard_cap);
         if (mid) (void)hipEventRecord(mid[1], s);
         if (f.flatten_coop)
-            hipLaunchKernelGGL((k_flatten_heavy<true, CULL>), dim3(grid_heavy), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
+            hipLaunchKernelGGL((k_flatten_heavy<true, CULL>), dim3(grid_heavy), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                                f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap);
         else
-            hipLaunchKernelGGL((k_flatten_heavy<false, CULL>), dim3(grid_heavy), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
+            hipLaunchKernelGGL((k_flatten_heavy<false, CULL>), dim3(grid_heavy), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                                f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap);
     }
 }

@@ -352,6 +352,17 @@ int vh_renderer_render_to_texture_on(void *r, void *scene, void *texture, size_t
     p.antialiasing_method = (vello::AaConfig)aa;
     return ((vello::Renderer *)r)->render_to_texture(((SceneHandle *)scene)->scene, texture, stride, is_device != 0, p, src_stream);
 }
+// ... and with RenderParams::view (nullable: six floats, vello_hip_set_view_transform's layout)
+int vh_renderer_render_to_texture_view(void *r, void *scene, void *texture, size_t stride, int is_device, uint32_t width, uint32_t height,
+                                       const float *base_color, uint32_t aa, void *src_stream, const float *view) {
+    vello::RenderParams p;
+    p.base_color = color_from(base_color);
+    p.width = width;
+    p.height = height;
+    p.antialiasing_method = (vello::AaConfig)aa;
+    if (view) p.view = std::array<float, 6>{view[0], view[1], view[2], view[3], view[4], view[5]};
+    return ((vello::Renderer *)r)->render_to_texture(((SceneHandle *)scene)->scene, texture, stride, is_device != 0, p, src_stream);
+}
 // Renderer::override_image: has_source = 0 removes the override.  Returns 1 and the previous source in prev[0..1] if there was one.
 int vh_renderer_override_image(void *r, uint64_t image_id, int has_source, uint64_t src, uint64_t stride, uint64_t prev[2]) {
     vello_encoding::ImageData image;

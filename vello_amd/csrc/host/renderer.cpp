@@ -85,8 +85,16 @@ int Renderer::render_to_texture(const Scene &scene, void *texture, size_t stride
     static_assert(sizeof(l) == sizeof(layout), "Layout");
     std::memcpy(&l, &layout, sizeof l);
     vello_hip_render_params p{params.width, params.height, params.base_color.premul_rgba8(), (uint32_t)params.antialiasing_method};
+    if (params.view) {
+        int vr = vello_hip_set_view_transform(ctx_, params.view->data());
+        if (vr != VELLO_HIP_OK) {
+            error_ = vello_hip_last_error(ctx_);
+            return vr;
+        }
+    }
     int r = vello_hip_render(ctx_, packed_.data(), packed_.size(), &l, &p, res.ramps, res.n_ramps, texture, stride, is_device ? 1 : 0, &bump_);
     if (r != VELLO_HIP_OK) error_ = vello_hip_last_error(ctx_);
+    if (params.view) (void)vello_hip_set_view_transform(ctx_, nullptr);  // (the frame's view, not the renderer's)
     return r;
 }
 

@@ -3,6 +3,7 @@
 // WgpuEngine::run_recording.  In the real drop-in this class is the Rust `Renderer` with its
 // `engine` field swapped for the FFI binding shown in INTEGRATION.md.
 #pragma once
+#include <array>
 #include <optional>
 #include <string>
 #include <unordered_map>
@@ -19,6 +20,9 @@ struct RenderParams {
     Color base_color{0.f, 0.f, 0.f, 1.f};
     uint32_t width = 0, height = 0;
     AaConfig antialiasing_method = AaConfig::Area;
+    // A view transform for this frame (vello_hip_set_view_transform: a vello_encoding::Transform, [m0 m1 m2 m3 t0 t1], composed in
+    // front of every transform of the scene on the GPU); none by default.  It holds for this frame only.
+    std::optional<std::array<float, 6>> view;
 };
 
 // What Renderer::override_image binds to an image id in place of its pixels (upstream: a wgpu texture, its origin and mip

@@ -30,8 +30,22 @@ E_CAPACITY = -4
 
 
 class RenderParams:
-    def __init__(self, base_color, width, height, antialiasing_method=AaConfig.Area):
+    """`view` (an Affine, or six floats [m0 m1 m2 m3 t0 t1]; default None) is a view transform for this frame only: the engine
+    composes it in front of every transform of the scene (vello_hip_set_view_transform)."""
+
+    def __init__(self, base_color, width, height, antialiasing_method=AaConfig.Area, view=None):
         self.base_color, self.width, self.height, self.antialiasing_method = base_color, width, height, antialiasing_method
+        self.view = view
+
+
+def _view_floats(view):
+    """Transform::from_kurbo (vello_encoding/src/math.rs): the six coefficients of an Affine (or six numbers) as f32."""
+    if view is None:
+        return None
+    coeffs = view.c if hasattr(view, "c") else tuple(view)
+    if len(coeffs) != 6:
+        raise ValueError("a view transform has six coefficients [m0 m1 m2 m3 t0 t1]")
+    return (ctypes.c_float * 6)(*[float(v) for v in coeffs])
 
 
 class RendererOptions:
@@ -132,8 +146,9 @@ class Renderer:
             import torch
 
             src_stream, relay = _source_stream(torch.cuda.current_stream())
-        r = self._lib.vh_renderer_render_to_texture_on(self._h, scene._h, ptr, stride, 1 if is_dev else 0, params.width, params.height,
-                                                       params.base_color._ptr(), int(params.antialiasing_method), src_stream)
+        r = self._lib.vh_renderer_render_to_texture_view(self._h, scene._h, ptr, stride, 1 if is_dev else 0, params.width, params.height,
+                                                         params.base_color._ptr(), int(params.antialiasing_method), src_stream,
+                                                         _view_floats(getattr(params, "view", None)))
         if relay is not None:
             relay[0].wait_stream(relay[1])
         if r != 0:
@@ -331,6 +346,12 @@ class Engine:
         Applies to frames enqueued after the call."""
         self._check(self._lib.vello_hip_set_viewport_cull(self._h, 1 if enabled else 0), "set_viewport_cull")
 
+    def set_view_transform(self, view=None):
+        """vello_hip_set_view_transform: frames enqueued from here on are rendered as if every transform T of the scene were
+        view . T (an Affine, or six floats [m0 m1 m2 m3 t0 t1]); None switches it off.  The resident scene is not modified, and
+        frames already enqueued keep the view they were enqueued with."""
+        self._check(self._lib.vello_hip_set_view_transform(self._h, _view_floats(view)), "set_view_transform")
+
     def set_debug_flags(self, no_cull=False, stroke_kernel=False, seq_clip=False, fine_slices=False, flatten_coop=False, flatten_alone=False, no_fusion=False):
         """vello_hip_set_debug_flags: no_cull makes coarse emit every draw (reference-exact PTCL / segments); stroke_kernel
         runs flatten's stroked-line kernel whatever the number of stroked lines; seq_clip matches clips with the one-wave
@@ -359,6 +380,10 @@ class Engine:
     def fused_launches(self):
         """vello_hip_fused_launches: launches in which stages of a small scene shared a kernel, since the engine was created."""
         return int(self._lib.vello_hip_fused_launches(self._h))
+
+    def scene_allocations(self):
+        """vello_hip_scene_allocations: scene buffers allocated since the engine was created."""
+        return int(self._lib.vello_hip_scene_allocations(self._h))
 
     def set_frames_in_flight(self, n):
         self._check(self._lib.vello_hip_set_frames_in_flight(self._h, n), "set_frames_in_flight")
@@ -438,14 +463,19 @@ class Engine:
         return out
 
 
-def estimate_capacities(packed, layout, width, height):
-    """vello_hip_estimate_capacities: conservative pool sizes (dict) for a packed scene at a target size (host only)."""
+def estimate_capacities(packed, layout, width, height, view=None):
+    """vello_hip_estimate_capacities: conservative pool sizes (dict) for a packed scene at a target size (host only); with
+    `view` (as Engine.set_view_transform takes it), vello_hip_estimate_capacities_view: for the scene under that view."""
     lib = load_library()
     packed = np.ascontiguousarray(packed, dtype=np.uint8)
     lay = LayoutStruct(*layout)
     p = RenderParamsStruct(width, height, 0, 0)
     c = Capacities()
-    r = lib.vello_hip_estimate_capacities(packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p), ctypes.byref(c))
+    if view is None:
+        r = lib.vello_hip_estimate_capacities(packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p), ctypes.byref(c))
+    else:
+        r = lib.vello_hip_estimate_capacities_view(packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p), _view_floats(view),
+                                                   ctypes.byref(c))
     if r != 0:
         raise VelloHipError(f"vello_hip_estimate_capacities failed ({r})")
     return {k: getattr(c, k) for k, _ in Capacities._fields_}
