@@ -23,6 +23,8 @@
  *   vello_hip_copy_images_device  the image_overrides branch of         vello/src/wgpu_engine.rs:486-504,
  *                              Command::WriteImage (copy_texture_to_texture) vello/src/lib.rs:536-555
  *                              for Renderer::override_image / register_texture
+ *   vello_hip_upload_fragments /  Scene::append(&other, Some(transform))  vello/src/scene.rs (append),
+ *   vello_hip_render_instances    per instance + resolve + upload        vello_encoding/src/encoding.rs:95-152
  *   vello_hip_sync             queue.submit + device.poll                vello/src/wgpu_engine.rs:757
  *   vello_hip_set_frames_in_flight  back-to-back queue.submit without waiting  vello/src/wgpu_engine.rs:757
  *   vello_hip_get_bump         the robust path's bump download           vello/src/lib.rs:730, :753-761
@@ -294,6 +296,73 @@ int vello_hip_set_view_transform(vello_hip_ctx *ctx, const float view[6] /* null
 int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                                        const vello_hip_render_params *params, const float view[6] /* nullable */,
                                        vello_hip_capacities *out);
+
+/* Scene instances: the resident scene as a library of fragments, a frame as a list of (fragment, transform) pairs -- what a host
+ * builds with Scene::append(&fragment, Some(transform)) per pair (vello_encoding/src/encoding.rs:95-152), composed on the GPU. */
+/* (The two structs below are declared tag first, typedef after -- to C the same as `typedef struct X {...} X;` -- because the
+ * struct parser of tests/test_shim.py, which reads every `typedef struct ... {` of this header, has no rule for array fields;
+ * tests/test_scene_instances_emu.py holds these two to their ctypes and Rust mirrors.) */
+/* Half-open ranges [begin, end) into the six streams of the resident scene. */
+struct vello_hip_fragment {
+    uint32_t path_tags[2];   /* tags (bytes) from the start of the tag stream          */
+    uint32_t path_data[2];   /* words from path_data_base                               */
+    uint32_t draws[2];       /* draw objects (= paths): index the draw tags             */
+    uint32_t draw_data[2];   /* words from draw_data_base                               */
+    uint32_t transforms[2];  /* entries of 6 words                                      */
+    uint32_t styles[2];      /* entries of 2 words                                      */
+};
+typedef struct vello_hip_fragment vello_hip_fragment;
+/* A fragment placed by `transform`, a vello_encoding::Transform [m0 m1 m2 m3 t0 t1] as vello_hip_set_view_transform takes it. */
+struct vello_hip_instance {
+    uint32_t fragment;
+    float transform[6];
+};
+typedef struct vello_hip_instance vello_hip_instance;
+
+/* vello_hip_upload_scene plus a table of `n_frags` fragments of that scene.  The scene is an ordinary resident scene
+ * (vello_hip_render_resident shows it whole); a later vello_hip_upload_scene -- vello_hip_render's included -- drops the table.
+ * Every fragment is checked against the host bytes; VELLO_HIP_E_INVALID (vello_hip_last_error names the fragment), with NOTHING
+ * left resident, unless for each one
+ *   - every range is ordered and lies inside its stream;
+ *   - `draws` is as long as the tag range has PATH markers, `transforms` / `styles` as it has TRANSFORM / STYLE markers;
+ *   - `draw_data` is as long as the fragment's draw tags ask for;
+ *   - its clips are balanced, no prefix of its draw tags holding more END_CLIP than BEGIN_CLIP;
+ *   - a TRANSFORM and a STYLE marker precede its first segment or PATH tag (a Scene that begins with a fill, a stroke or a
+ *     filled layer satisfies this): no fragment reads transform -1 or a neighbour's style.
+ * Whether the path data matches the tags is, as for any scene, the pathtag scan's to find (VELLO_HIP_E_INVALID at sync). */
+int vello_hip_upload_fragments(vello_hip_ctx *ctx, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                               const uint32_t *ramps, uint32_t n_ramps, const vello_hip_fragment *frags, uint32_t n_frags);
+/* The composed scene of instances i = 0 .. n-1, F(i) the fragment of instance i and V_i its transform:
+ *   tags       the concatenation of the F(i)'s tag bytes, zero-padded to a multiple of 1024 bytes (none for no tags);
+ *   then, in this order, the concatenations of the F(i)'s path-data words, draw tags, draw-data words, transform entries
+ *   and style entries.
+ *   1. Every transform entry T of instance i becomes V_i.T, by the formula and in the arithmetic of
+ *      vello_hip_set_view_transform: f32, every product and every sum rounded on its own.  No other word changes.
+ *   2. Layout: path_tag_base = 0, the five other bases are the running sums; n_paths = n_draw_objects = the sum of the `draws`
+ *      lengths, n_clips = the fragments' clip tags, bin_data_start = their info words; scene_len = 4 * (style_base + 2 * styles).
+ *   3. Gradient ramps and the image atlas are the library's (the draw data carries the library's ramp ids and atlas
+ *      coordinates verbatim).
+ * vello_hip_instances_layout returns exactly this layout and length on the host, without touching the GPU.
+ * VELLO_HIP_E_INVALID for both entry points -- vello_hip_render_instances then enqueues nothing and leaves the rotation of the
+ * in-flight buffer sets where it was -- when there is no fragment table, `inst` is NULL with n > 0, a fragment index is out of
+ * range, a transform has a NaN or infinite entry, or the composed scene has 2^32 words or more or a count that leaves u32. */
+int vello_hip_instances_layout(vello_hip_ctx *ctx, const vello_hip_instance *inst, uint32_t n, vello_hip_layout *layout_out,
+                               size_t *scene_len_out);
+/* vello_hip_render_frame with the frame's scene composed on the GPU: takes the next in-flight buffer set (waiting for that set's
+ * previous frame only), copies a table of 52 bytes per instance through pinned memory, has ONE kernel (k_compose_scene) write the
+ * composed scene into the set's private scene slot -- where vello_hip_render_frame copies host bytes -- enqueues every stage and
+ * returns without waiting.  `inst` may be reused when the call returns.
+ *   1. n == 0 renders the base colour.
+ *   2. Composes with vello_hip_set_view_transform (applied on top: a transform entry ends up as View.(V_i.T)) and with
+ *      vello_hip_set_viewport_cull, like a vello_hip_render_frame scene.
+ *   3. Afterwards VELLO_HIP_BUF_SCENE / VELLO_HIP_BUF_CONFIG show the composed bytes and layout of the last frame and
+ *      vello_hip_run_stages acts on them, as after vello_hip_render_frame.  The library's bytes are never modified.
+ *   4. A pool overflow is reported as for vello_hip_render_frame: VELLO_HIP_E_CAPACITY at vello_hip_sync, the counters through
+ *      vello_hip_get_bump; vello_hip_grow_pools and a second call render the frame again.
+ * Out of scope: pool estimation for instance lists (vello_hip_estimate_capacities needs host bytes; with vello_hip_set_auto_grow
+ * only the PTCL / info-word minimum of the target is sized), ramps or atlases per fragment, and unbalanced fragments. */
+int vello_hip_render_instances(vello_hip_ctx *ctx, const vello_hip_instance *inst, uint32_t n, const vello_hip_render_params *params,
+                               void *out_device, size_t out_stride);
 
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a
  * later opaque full-tile cover is normally not emitted; the image is the same, but bump.segments / bump.ptcl and the

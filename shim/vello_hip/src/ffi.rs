@@ -71,6 +71,26 @@ pub struct vello_hip_image_copy {
     pub height: u32,
 }
 
+/// Half-open `[begin, end)` ranges of one fragment in the six streams of the resident scene (`vello_hip_upload_fragments`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vello_hip_fragment {
+    pub path_tags: [u32; 2],
+    pub path_data: [u32; 2],
+    pub draws: [u32; 2],
+    pub draw_data: [u32; 2],
+    pub transforms: [u32; 2],
+    pub styles: [u32; 2],
+}
+
+/// One instance of `vello_hip_render_instances`: a fragment index and its transform `[m0 m1 m2 m3 t0 t1]`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct vello_hip_instance {
+    pub fragment: u32,
+    pub transform: [f32; 6],
+}
+
 pub const VELLO_HIP_AA_AREA: u32 = 0;
 pub const VELLO_HIP_AA_MSAA8: u32 = 1;
 pub const VELLO_HIP_AA_MSAA16: u32 = 2;
@@ -100,6 +120,9 @@ unsafe extern "C" {
     pub fn vello_hip_upload_scene(ctx: *mut vello_hip_ctx, scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, ramps: *const u32, n_ramps: u32) -> c_int;
     pub fn vello_hip_render_resident(ctx: *mut vello_hip_ctx, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_render_frame(ctx: *mut vello_hip_ctx, scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, params: *const vello_hip_render_params, ramps: *const u32, n_ramps: u32, out_device: *mut c_void, out_stride: usize) -> c_int;
+    pub fn vello_hip_upload_fragments(ctx: *mut vello_hip_ctx, scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, ramps: *const u32, n_ramps: u32, frags: *const vello_hip_fragment, n_frags: u32) -> c_int;
+    pub fn vello_hip_instances_layout(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, n: u32, layout_out: *mut vello_hip_layout, scene_len_out: *mut usize) -> c_int;
+    pub fn vello_hip_render_instances(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, n: u32, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_resize_image_atlas(ctx: *mut vello_hip_ctx, width: u32, height: u32) -> c_int;
     pub fn vello_hip_write_image(ctx: *mut vello_hip_ctx, x: u32, y: u32, width: u32, height: u32, rgba8: *const u8, stride: usize) -> c_int;
     pub fn vello_hip_copy_images_device(ctx: *mut vello_hip_ctx, copies: *const vello_hip_image_copy, n: u32, src_stream: *mut c_void) -> c_int;

@@ -47,6 +47,14 @@ class ImageCopyStruct(ctypes.Structure):  # vello_hip_image_copy
     _fields_ = [("src", ctypes.c_uint64), ("src_stride", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in ("x", "y", "width", "height")]
 
 
+class FragmentStruct(ctypes.Structure):  # vello_hip_fragment: half-open [begin, end) ranges into the six streams
+    _fields_ = [(n, ctypes.c_uint32 * 2) for n in ("path_tags", "path_data", "draws", "draw_data", "transforms", "styles")]
+
+
+class InstanceStruct(ctypes.Structure):  # vello_hip_instance
+    _fields_ = [("fragment", ctypes.c_uint32), ("transform", ctypes.c_float * 6)]
+
+
 def load_library():
     """Loads the product library; raises (never falls back) when it is missing."""
     global _LIB
@@ -86,6 +94,9 @@ def load_library():
     sig("vello_hip_upload_scene", i32, [vp, vp, sz, c.POINTER(LayoutStruct), vp, u32])
     sig("vello_hip_render_frame", i32, [vp, vp, sz, c.POINTER(LayoutStruct), c.POINTER(RenderParamsStruct), vp, u32, vp, sz])
     sig("vello_hip_render_resident", i32, [vp, c.POINTER(RenderParamsStruct), vp, sz])
+    sig("vello_hip_upload_fragments", i32, [vp, vp, sz, c.POINTER(LayoutStruct), vp, u32, c.POINTER(FragmentStruct), u32])
+    sig("vello_hip_instances_layout", i32, [vp, vp, u32, c.POINTER(LayoutStruct), c.POINTER(sz)])
+    sig("vello_hip_render_instances", i32, [vp, vp, u32, c.POINTER(RenderParamsStruct), vp, sz])
     sig("vello_hip_set_frames_in_flight", i32, [vp, u32])
     sig("vello_hip_resize_image_atlas", i32, [vp, u32, u32])
     sig("vello_hip_write_image", i32, [vp, u32, u32, u32, u32, vp, sz])

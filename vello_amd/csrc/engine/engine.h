@@ -258,4 +258,28 @@ static_assert(sizeof(AtlasCopyDesc) == 40, "AtlasCopyDesc");
 // `descs`: n entries in device memory, `total` = the last entry's first + its texels (> 0)
 void launch_atlas_copy(const AtlasCopyDesc *descs, uint32_t n, uint64_t total, uint32_t *atlas, uint32_t atlas_w, hipStream_t s);
 
+// Scene instances (vello_hip_render_instances, engine.hip): what k_compose_scene is handed by value.  Streams are numbered in the order
+// the packed scene holds them: 0 path tags, 1 path data, 2 draw tags, 3 draw data, 4 transforms, 5 styles.  Every offset is in u32 words
+// but the tag stream's, which are in bytes.
+//   table: [6][n + 1] exclusive prefixes of the instances' lengths per stream -- one stream's offsets are consecutive words, so a
+//          search over them reads one run of memory -- then [n] fragment indices, then [n][6] transforms (COMPOSE_TABLE_WORDS);
+//   frags: [n_frags][6] where each fragment's range begins in the library's stream.
+// The grid is cut per stream (wg_first): a workgroup's chunk of steps x 256 words lies in ONE stream, so it needs one slice of one
+// prefix; the last workgroup writes the 16 words of zero slack behind the scene.
+constexpr uint32_t COMPOSE_MAX_STEPS = 8u, COMPOSE_TARGET_WGS = 2048u;
+struct ComposeArgs {
+    const uint32_t *lib;    // the library: the resident scene
+    uint32_t *dst;          // the lane's private scene slot
+    const uint32_t *table;
+    const uint32_t *frags;
+    uint32_t n, steps;
+    uint32_t src_base[6];   // the library's layout bases
+    uint32_t dst_base[6];   // the composed layout's
+    uint32_t len[6];        // words of each composed stream (the tag stream's with its padding)
+    uint32_t wg_first[7];   // first workgroup of each stream; [6]: the slack's
+    uint32_t tag_bytes;     // tags of the composed scene, without the padding
+};
+inline size_t compose_table_words(uint32_t n) { return 6u * ((size_t)n + 1u) + 7u * (size_t)n; }
+void launch_compose_scene(const ComposeArgs &a, hipStream_t s);
+
 }  // namespace vk

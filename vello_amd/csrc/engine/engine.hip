@@ -98,6 +98,116 @@ void launch_view_transforms(const Frame &f, hipStream_t s) {
                        const_cast<uint32_t *>(f.scene) + (f.xf_base - 6u));
 }
 
+// k_compose_scene: a frame's packed scene written from instances of the library's fragments (vello_hip_render_instances; the contract is
+// in include/vello_hip.h, the arguments in engine.h).  A thread per destination word, a workgroup per chunk of steps x 256 consecutive
+// words of ONE stream, lane i of a wave on word base + i as in k_atlas_copy.  Which instance a word belongs to is a search for the last
+// entry of the stream's prefix that is <= the word's offset (empty instances repeat an offset; the last one of a run is the one that
+// holds words).  Fragments may be a dozen words long, so the search is the cost: threads 0 and 64 find the chunk's first and last
+// instance in the table, the workgroup copies that slice of the prefix into LDS, and every thread searches the slice, from the
+// instance of its previous word on.  The staging area holds an entry per word of the largest chunk plus two, which is every slice of
+// a word stream without empty instances (an instance that holds words holds at least one).  A slice can be longer where empty
+// instances lie in between and, in the tag stream, where fragments are shorter than four tags (a word holds up to four one-tag
+// instances): such a chunk is not staged and its threads search the table itself.
+//   word streams   a dword copy from the library;
+//   transforms     word k of an entry needs two words of T and two or three of V: V.T as k_view_transforms computes it;
+//   tags           byte-granular: where the four tags of a word come from one instance, two dword loads and a funnel shift; a word
+//                  that straddles instances (or the stream's end) is put together from byte loads.  Words of the padding are zero.
+constexpr uint32_t COMPOSE_LDS_OFFSETS = COMPOSE_MAX_STEPS * 256u + 2u;
+
+__global__ void __launch_bounds__(256) k_compose_scene(ComposeArgs a) {
+    __shared__ uint32_t s_off[COMPOSE_LDS_OFFSETS];
+    __shared__ uint32_t s_ends[2];
+    const uint32_t bid = blockIdx.x, tid = threadIdx.x;
+    uint32_t s = 0u;
+#pragma unroll
+    for (uint32_t k = 1u; k < 7u; k++) s += a.wg_first[k] <= bid ? 1u : 0u;  // (non-decreasing: the last stream that starts at or before bid)
+    if (s == 6u) {
+        if (tid < 16u) a.dst[(size_t)a.dst_base[5] + a.len[5] + tid] = 0u;
+        return;
+    }
+    const uint32_t chunk = a.steps * 256u;
+    const uint32_t lo = (bid - a.wg_first[s]) * chunk;                         // < len[s]: the host launches ceil(len / chunk) workgroups
+    const uint32_t rem = a.len[s] - lo < chunk ? a.len[s] - lo : chunk;        // words of this chunk
+    // the chunk in the units of the stream's prefix (bytes for tags: the host keeps the padded tag bytes within u32)
+    const uint32_t ulo = s == 0u ? lo * 4u : lo;
+    uint32_t uend = s == 0u ? (lo + rem) * 4u : lo + rem;
+    if (s == 0u && uend > a.tag_bytes) uend = a.tag_bytes;
+    const bool any = ulo < uend;  // (else: a chunk of the tags' padding)
+    const uint32_t *off = a.table + (size_t)s * (a.n + 1u);
+    const uint32_t *frag_of = a.table + 6u * ((size_t)a.n + 1u);
+    if (any && (tid == 0u || tid == 64u)) {
+        const uint32_t x = tid == 0u ? ulo : uend - 1u;
+        uint32_t i = 0u, h = a.n - 1u;  // (any: some instance holds x, so n > 0)
+        while (i < h) {
+            const uint32_t mid = (i + h + 1u) >> 1;
+            if (off[mid] <= x) i = mid;
+            else h = mid - 1u;
+        }
+        s_ends[tid >> 6] = i;
+    }
+    __syncthreads();
+    const uint32_t first = any ? s_ends[0] : 0u, last = any ? s_ends[1] : 0u;
+    const uint32_t m = last - first + 2u;  // off[first .. last + 1]
+    const bool staged = any && m <= COMPOSE_LDS_OFFSETS;
+    if (staged)
+        for (uint32_t k = tid; k < m; k += 256u) s_off[k] = off[first + k];
+    __syncthreads();
+    auto at = [&](uint32_t i) -> uint32_t { return staged ? s_off[i - first] : off[i]; };  // first <= i <= last + 1
+    uint32_t cur = first;
+    for (uint32_t k = 0u; k < a.steps; k++) {
+        const uint32_t idx = k * 256u + tid;
+        if (idx >= rem) break;
+        const uint32_t l = lo + idx;
+        uint32_t *d = a.dst + (size_t)a.dst_base[s] + l;
+        const uint32_t x = s == 0u ? l * 4u : l;
+        if (x >= uend) {  // the tags' padding
+            *d = 0u;
+            continue;
+        }
+        uint32_t i = cur, h = last;
+        while (i < h) {
+            const uint32_t mid = (i + h + 1u) >> 1;
+            if (at(mid) <= x) i = mid;
+            else h = mid - 1u;
+        }
+        cur = i;
+        const uint32_t o = at(i);
+        const uint32_t begin = a.frags[(size_t)frag_of[i] * 6u + s];
+        if (s == 0u) {
+            if (x + 4u <= at(i + 1u)) {
+                const uint32_t sb = begin + (x - o);  // byte of the library's tag stream
+                const uint32_t *p = a.lib + (size_t)a.src_base[0] + (sb >> 2);
+                const uint32_t sh = (sb & 3u) * 8u;
+                const uint32_t w0 = p[0], w1 = sh ? p[1] : 0u;
+                *d = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
+            } else {
+                const uint8_t *tags = reinterpret_cast<const uint8_t *>(a.lib + (size_t)a.src_base[0]);
+                uint32_t v = 0u, j = i;
+                for (uint32_t b = 0u; b < 4u; b++) {
+                    const uint32_t pos = x + b;
+                    if (pos >= uend) break;  // (the stream's end: uend == tag_bytes here)
+                    while (pos >= at(j + 1u)) j++;  // (pos < uend: an instance <= last holds it)
+                    v |= (uint32_t)tags[(size_t)a.frags[(size_t)frag_of[j] * 6u] + (pos - at(j))] << (8u * b);
+                }
+                *d = v;
+            }
+        } else if (s == 4u) {
+            const uint32_t r = x - o, comp = r % 6u, pair = comp >> 1, odd = comp & 1u;
+            const uint32_t *t = a.lib + (size_t)a.src_base[4] + begin + (r - comp) + 2u * pair;
+            const uint32_t *v = frag_of + a.n + (size_t)i * 6u;
+            float c = __uint_as_float(v[odd]) * __uint_as_float(t[0]) + __uint_as_float(v[2u + odd]) * __uint_as_float(t[1]);
+            if (pair == 2u) c = c + __uint_as_float(v[4u + odd]);
+            *d = __float_as_uint(c);
+        } else {
+            *d = a.lib[(size_t)a.src_base[s] + begin + (x - o)];
+        }
+    }
+}
+
+void launch_compose_scene(const ComposeArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(k_compose_scene, dim3(a.wg_first[6] + 1u), dim3(256), 0, s, a);
+}
+
 }  // namespace vk
 
 namespace {
@@ -146,6 +256,15 @@ struct SceneSlot {
     size_t view_at = 0;
     size_t view_cap_bytes = 0;  // bytes allocated from view_at on (ensure_scene)
     uint32_t view_sets = 0, view_set_words = 0;
+    // the bytes were composed from the library's fragments (vello_hip_render_instances): ramps are the shared slot's
+    bool composed = false;
+};
+// A fragment of the library as the host keeps it: where its range begins in each stream and how long it is -- in the units of
+// ComposeArgs (bytes for tags, words otherwise) -- and what the composed layout and fine's specialisation need of its draw tags.
+struct FragmentInfo {
+    uint32_t begin[6], len[6];
+    uint32_t n_clips, info_words;
+    bool brushes;
 };
 constexpr uint32_t MAX_LANES = 8;
 
@@ -162,6 +281,7 @@ struct Lane {
     DevBuf slice_items, slice_counters, cov;  // coarse -> fine: slices of long tiles, their arrival counters, coverage scratch
     DevBuf heavy_list;                // flatten: tag indices for the heavy code, 4 lists (one u32 per tag each, worst case)
     DevBuf arc_items;                 // flatten: arcs the stroke workgroups leave to the heavy code (64 B per segment, worst case)
+    DevBuf compose_table;             // vello_hip_render_instances: the frame's ComposeArgs::table
     DevBuf front_sync;                // k_front's grid-barrier counter (zeroed once, when allocated)
     uint32_t front_sync_value = 0;    // ... and its value once every launch enqueued so far has run
     struct EvPair {
@@ -195,6 +315,10 @@ struct vello_hip_ctx {
     DevBuf config;
     DevBuf mask8, mask16;
     SceneSlot shared;  // vello_hip_upload_scene: one scene for every lane
+    // vello_hip_upload_fragments: the shared scene as a library of fragments (dropped by the next vello_hip_upload_scene)
+    std::vector<FragmentInfo> fragments;
+    bool have_fragments = false;
+    DevBuf frag_table;  // ComposeArgs::frags
     DevBuf atlas;  // persistent image atlas (render.rs:160-176), shared by all lanes
     uint32_t atlas_w = 0, atlas_h = 0;
     std::vector<Lane> lanes;
@@ -222,6 +346,7 @@ struct vello_hip_ctx {
     // last frame
     Config cfg{};
     bool have_cfg = false;
+    bool cfg_unsent = false;  // `cfg` is newer than the device copy (vello_hip_render_instances): sent when VELLO_HIP_BUF_CONFIG is next touched
     // profiling
     uint32_t prof_mask = 0;
     std::vector<hipEvent_t> event_pool;
@@ -274,7 +399,9 @@ int sync_all(vello_hip_ctx *c) {
 // waits for the atlas uploads still in flight (before the atlas is freed / resized / the context goes away)
 int sync_uploads(vello_hip_ctx *c) {
     if (c->upload_stream) HIP_TRY(c, hipStreamSynchronize(c->upload_stream));
-    for (auto &st : c->staging) st.busy = false;
+    // (a block that carries a lane's instance table is released by its own event: the lane's stream is not waited for here)
+    for (auto &st : c->staging)
+        if (st.busy && hipEventQuery(st.done) == hipSuccess) st.busy = false;
     return 0;
 }
 
@@ -302,6 +429,7 @@ int acquire_staging(vello_hip_ctx *c, size_t bytes, Staging *&out) {
     if (held > ((size_t)256 << 20)) {  // bound the pinned memory: drain and start over
         int r = sync_uploads(c);
         if (r) return r;
+        if ((r = sync_all(c))) return r;  // (instance tables are copied on the lanes' streams)
         for (auto &st : c->staging) {
             (void)hipHostFree(st.host);
             (void)hipEventDestroy(st.done);
@@ -516,7 +644,10 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
         f.slice_cap = want > n_tiles_target ? n_tiles_target : (uint32_t)want;
     }
     // kernels take the ConfigUniform by value (kernarg); the device copy only serves the test seam
-    if (upload_cfg) HIP_TRY(c, hipMemcpy(c->config.ptr, &f.cfg, sizeof(Config), hipMemcpyHostToDevice));
+    if (upload_cfg) {
+        HIP_TRY(c, hipMemcpy(c->config.ptr, &f.cfg, sizeof(Config), hipMemcpyHostToDevice));
+        c->cfg_unsent = false;
+    }
     f.n_tag_words = sc.n_tag_words;
     f.n_scene_words = (uint32_t)(sc.scene_len / 4u);
     f.aa = p->aa;
@@ -570,8 +701,9 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
         f.output = (uint8_t *)l.buf[VELLO_HIP_BUF_OUTPUT].ptr;
         f.out_stride = (size_t)p->width * 4u;
     }
-    f.ramps = sc.n_ramps ? (const uint32_t *)sc.ramps.ptr : nullptr;
-    f.n_ramps = sc.n_ramps;
+    const SceneSlot &rs = sc.composed ? c->shared : sc;  // (a composed scene's draw data holds the library's ramp ids)
+    f.ramps = rs.n_ramps ? (const uint32_t *)rs.ramps.ptr : nullptr;
+    f.n_ramps = rs.n_ramps;
     f.brushes = sc.brushes || c->force_brushes;
     f.no_cull = (c->debug_flags & VELLO_HIP_DEBUG_NO_CULL) != 0u;
     f.viewport_cull = c->viewport_cull;
@@ -778,6 +910,14 @@ int drain_events(vello_hip_ctx *c) {
     return 0;
 }
 
+// brings the device copy of the Config up to the last frame's (vello_hip_render_instances leaves it to the reader)
+int send_config(vello_hip_ctx *c) {
+    if (!c->cfg_unsent) return 0;
+    HIP_TRY(c, hipMemcpy(c->config.ptr, &c->cfg, sizeof(Config), hipMemcpyHostToDevice));
+    c->cfg_unsent = false;
+    return 0;
+}
+
 DevBuf *find_buf(vello_hip_ctx *c, int id) {
     if (id == VELLO_HIP_BUF_SCENE) return &slot_of(c, c->lanes[c->last_lane]).scene;
     if (id == VELLO_HIP_BUF_CONFIG) return &c->config;
@@ -949,15 +1089,17 @@ void vello_hip_destroy(vello_hip_ctx *c) {
             if (b->ptr) (void)hipFree(b->ptr);
         if (l.heavy_list.ptr) (void)hipFree(l.heavy_list.ptr);
         if (l.arc_items.ptr) (void)hipFree(l.arc_items.ptr);
+        if (l.compose_table.ptr) (void)hipFree(l.compose_table.ptr);
         if (l.stream) (void)hipStreamDestroy(l.stream);
     }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
+    // (the lanes' streams were waited for above: instance tables travel on them, with or without an upload stream)
+    if (c->upload_stream) (void)hipStreamSynchronize(c->upload_stream);
+    for (auto &st : c->staging) {
+        (void)hipHostFree(st.host);
+        (void)hipEventDestroy(st.done);
+    }
     if (c->upload_stream) {
-        (void)hipStreamSynchronize(c->upload_stream);
-        for (auto &st : c->staging) {
-            (void)hipHostFree(st.host);
-            (void)hipEventDestroy(st.done);
-        }
         (void)hipEventDestroy(c->atlas_ready);
         (void)hipEventDestroy(c->lane_mark);
         (void)hipStreamDestroy(c->upload_stream);
@@ -967,7 +1109,7 @@ void vello_hip_destroy(vello_hip_ctx *c) {
     for (auto &l : c->lanes)
         for (DevBuf *b : {&l.own.scene, &l.own.ramps})
             if (b->ptr) (void)hipFree(b->ptr);
-    for (DevBuf *b : {&c->shared.scene, &c->shared.ramps, &c->config, &c->mask8, &c->mask16, &c->atlas, &c->copy_descs})
+    for (DevBuf *b : {&c->shared.scene, &c->shared.ramps, &c->config, &c->mask8, &c->mask16, &c->atlas, &c->copy_descs, &c->frag_table})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -1019,10 +1161,8 @@ static int ensure_scene(vello_hip_ctx *c, SceneSlot &sc, size_t bytes, size_t ta
     return 0;
 }
 
-// Validates the layout, sizes the slot and copies scene + ramps on `st`; returns once the source buffers may be
-// reused (they are caller-owned only for the duration of the call, recording.rs:124-129).
-static int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *scene, size_t scene_len,
-                     const vello_hip_layout *layout, const uint32_t *ramps, uint32_t n_ramps) {
+// Whether `layout` describes a buffer of scene_len bytes (the streams' contents are judged by load_slot and the pathtag scan)
+static int check_layout(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout) {
     if ((!scene && scene_len) || !layout || (scene_len & 3u)) return VELLO_HIP_E_INVALID;
     const vello_hip_layout &L = *layout;
     size_t words = scene_len / 4u;
@@ -1036,6 +1176,12 @@ static int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint
         c->last_error = "path tag stream is not padded to 4*256 tags (resolve.rs:622-639)";
         return VELLO_HIP_E_INVALID;
     }
+    return VELLO_HIP_OK;
+}
+
+// Sizes the slot for a scene of this (checked) layout and length and forgets what earlier frames told of the scene it held: what
+// load_slot does before it copies the bytes, and vello_hip_render_instances before k_compose_scene writes them.
+static int size_slot(vello_hip_ctx *c, SceneSlot &sc, const vello_hip_layout &L, size_t scene_len) {
     int r;
     // 64 B of slack: flatten reads tag ix+1 and the (wrapped) style word of pre-style tags speculatively
     // ... and, behind them, room for the composed transform words of frames with a view (SceneSlot::view_at)
@@ -1055,11 +1201,23 @@ static int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint
     // Which fine specialisation the scene needs: any draw tag other than COLOR / BEGIN_CLIP / END_CLIP / NOP
     // (draw.rs:15-51) makes coarse emit a gradient, image or blur command.
     sc.brushes = false;
+    sc.composed = false;
     sc.stroke_lines = -1;
     sc.heavy_curves = sc.heavy_strokes = -1;
     sc.soup_lines = -1;
     sc.slice_demand = -1;
     sc.generation += 1u;
+    return VELLO_HIP_OK;
+}
+
+// Validates the layout, sizes the slot and copies scene + ramps on `st`; returns once the source buffers may be
+// reused (they are caller-owned only for the duration of the call, recording.rs:124-129).
+static int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *scene, size_t scene_len,
+                     const vello_hip_layout *layout, const uint32_t *ramps, uint32_t n_ramps) {
+    int r;
+    if ((r = check_layout(c, scene, scene_len, layout))) return r;
+    const vello_hip_layout &L = *layout;
+    if ((r = size_slot(c, sc, L, scene_len))) return r;
     {
         // The same pass checks what draw_leaf / clip_leaf will index with (shared/drawtag.wgsl:47-54: bit 0 = clip,
         // bits 2-4 = draw data words, bits 6-9 = info words).  WebGPU's robust buffer access absorbs an inconsistent
@@ -1102,6 +1260,8 @@ int vello_hip_upload_scene(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
     int r;
     // frames still in flight read the old scene
     if ((r = sync_all(c))) return r;
+    c->have_fragments = false;  // (vello_hip_upload_fragments sets its table once the scene is resident)
+    c->fragments.clear();
     if ((r = load_slot(c, c->shared, c->lanes[0].stream, scene, scene_len, layout, ramps, n_ramps))) return r;
     for (auto &l : c->lanes) {
         l.use_own = false;
@@ -1131,6 +1291,259 @@ int vello_hip_render_frame(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
     c->last_lane = li;
     Frame f;
     if ((r = prepare_frame(c, l, params, out_device, out_stride, f, false))) return r;
+    return run_stage_range(c, l, f, 0, VELLO_HIP_STAGE_FINE);
+}
+
+// One fragment against the host bytes of its (checked) library: the rules of vello_hip_upload_fragments in include/vello_hip.h.
+static int check_fragment(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout &L, const vello_hip_fragment &fr,
+                          uint32_t index, FragmentInfo &out) {
+    auto refuse = [&](const char *why) {
+        c->last_error = "upload_fragments: fragment " + std::to_string(index) + ": " + why;
+        return VELLO_HIP_E_INVALID;
+    };
+    const uint32_t *words = reinterpret_cast<const uint32_t *>(scene);
+    const uint64_t n_words = scene_len / 4u;
+    const uint32_t draws_room = L.draw_data_base - L.draw_tag_base;
+    // the streams' lengths and what one entry is in the units of ComposeArgs
+    const uint64_t stream_len[6] = {((uint64_t)L.path_data_base - L.path_tag_base) * 4u, (uint64_t)L.draw_tag_base - L.path_data_base,
+                                    L.n_draw_objects < draws_room ? L.n_draw_objects : draws_room, (uint64_t)L.transform_base - L.draw_data_base,
+                                    ((uint64_t)L.style_base - L.transform_base) / 6u, (n_words - L.style_base) / STYLE_SIZE_IN_WORDS};
+    const uint32_t unit[6] = {1u, 1u, 1u, 1u, 6u, STYLE_SIZE_IN_WORDS};
+    const uint32_t *range[6] = {fr.path_tags, fr.path_data, fr.draws, fr.draw_data, fr.transforms, fr.styles};
+    uint32_t n_entries[6];
+    for (int s = 0; s < 6; s++) {
+        if (range[s][0] > range[s][1] || range[s][1] > stream_len[s]) return refuse("a range is not ordered or leaves its stream");
+        n_entries[s] = range[s][1] - range[s][0];
+        out.begin[s] = range[s][0] * unit[s];  // (<= the stream's words: no overflow)
+        out.len[s] = n_entries[s] * unit[s];
+    }
+    const uint8_t *tags = scene + (size_t)L.path_tag_base * 4u;
+    uint32_t n_path = 0, n_xf = 0, n_style = 0;
+    bool has_xf = false, has_style = false;
+    for (uint32_t i = fr.path_tags[0]; i < fr.path_tags[1]; i++) {
+        const uint32_t t = tags[i];
+        if (((t & PATH_TAG_SEG_TYPE) != 0u || (t & PATH_TAG_PATH) != 0u) && !(has_xf && has_style))
+            return refuse("a segment or PATH tag comes before the fragment's first TRANSFORM and STYLE markers");
+        if (t & PATH_TAG_PATH) n_path++;
+        if (t & PATH_TAG_TRANSFORM) n_xf++, has_xf = true;
+        if (t & PATH_TAG_STYLE) n_style++, has_style = true;
+    }
+    if (n_path != n_entries[2]) return refuse("`draws` is not as long as the tag range has PATH markers");
+    if (n_xf != n_entries[4] || n_style != n_entries[5]) return refuse("`transforms` / `styles` are not as long as the tag range has TRANSFORM / STYLE markers");
+    uint64_t draw_data_words = 0, info_words = 0;
+    uint32_t clip_tags = 0, depth = 0;
+    out.brushes = false;
+    for (uint32_t i = fr.draws[0]; i < fr.draws[1]; i++) {
+        const uint32_t t = words[L.draw_tag_base + i];
+        if (t != DRAWTAG_FILL_COLOR && t != DRAWTAG_BEGIN_CLIP && t != DRAWTAG_END_CLIP && t != DRAWTAG_NOP) out.brushes = true;
+        clip_tags += t & 1u;
+        draw_data_words += (t >> 2) & 0x7u;
+        info_words += (t >> 6) & 0xfu;
+        if (t == DRAWTAG_BEGIN_CLIP) depth++;
+        if (t == DRAWTAG_END_CLIP) {
+            if (depth == 0u) return refuse("an END_CLIP without a BEGIN_CLIP before it in the fragment");
+            depth--;
+        }
+    }
+    if (depth != 0u) return refuse("a BEGIN_CLIP is left open");
+    if (draw_data_words != n_entries[3]) return refuse("`draw_data` is not as long as the fragment's draw tags ask for");
+    if (info_words > 0xffffffffull) return refuse("more than 2^32 info words");  // (up to 15 per draw tag)
+    out.n_clips = clip_tags;
+    out.info_words = (uint32_t)info_words;
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout, const uint32_t *ramps,
+                               uint32_t n_ramps, const vello_hip_fragment *frags, uint32_t n_frags) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // whatever goes wrong from here on, nothing stays resident (frames in flight keep what they were enqueued with)
+    c->shared.resident = false;
+    c->have_fragments = false;
+    c->fragments.clear();
+    if (n_frags > 0u && !frags) {
+        c->last_error = "upload_fragments: frags is NULL";
+        return VELLO_HIP_E_INVALID;
+    }
+    int r;
+    if ((r = check_layout(c, scene, scene_len, layout))) return r;
+    std::vector<FragmentInfo> infos(n_frags);
+    for (uint32_t i = 0; i < n_frags; i++)
+        if ((r = check_fragment(c, scene, scene_len, *layout, frags[i], i, infos[i]))) return r;
+    if ((r = vello_hip_upload_scene(c, scene, scene_len, layout, ramps, n_ramps))) return r;
+    // (the lanes are idle: upload_scene waited for them, so no frame reads the table that ensure() may free)
+    std::vector<uint32_t> begins((size_t)n_frags * 6u);
+    for (uint32_t i = 0; i < n_frags; i++) std::memcpy(&begins[(size_t)i * 6u], infos[i].begin, sizeof infos[i].begin);
+    if ((r = ensure(c, c->frag_table, begins.size() * 4u))) {
+        c->shared.resident = false;
+        return r;
+    }
+    if (n_frags) {
+        const hipError_t e = hipMemcpy(c->frag_table.ptr, begins.data(), begins.size() * 4u, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            c->shared.resident = false;
+            c->last_error = std::string("upload_fragments: ") + hipGetErrorString(e);
+            return VELLO_HIP_E_HIP;
+        }
+    }
+    c->fragments = std::move(infos);
+    c->have_fragments = true;
+    return VELLO_HIP_OK;
+}
+
+// The composed scene of an instance list: its layout, its length, what fine needs to know of it, and the sums the table is built from.
+struct ComposePlan {
+    vello_hip_layout layout;
+    size_t scene_len;
+    uint32_t len[6];      // per stream, in the units of ComposeArgs (tags: bytes, without the padding)
+    uint32_t tag_words;   // the tag stream with its padding
+    bool brushes;
+};
+
+static int plan_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, ComposePlan &p) {
+    if (!c->have_fragments || !c->shared.resident) {
+        c->last_error = "no fragment table (vello_hip_upload_fragments)";
+        return VELLO_HIP_E_INVALID;
+    }
+    if (n > 0u && !inst) {
+        c->last_error = "instances: inst is NULL";
+        return VELLO_HIP_E_INVALID;
+    }
+    uint64_t len[6] = {}, n_clips = 0, info = 0;
+    p.brushes = false;
+    const size_t n_frags = c->fragments.size();
+    for (uint32_t i = 0; i < n; i++) {
+        if (inst[i].fragment >= n_frags) {
+            c->last_error = "instance " + std::to_string(i) + ": fragment " + std::to_string(inst[i].fragment) + " of " + std::to_string(n_frags);
+            return VELLO_HIP_E_INVALID;
+        }
+        for (int k = 0; k < 6; k++)
+            if (!(inst[i].transform[k] - inst[i].transform[k] == 0.0f)) {  // NaN or infinity
+                c->last_error = "instance " + std::to_string(i) + ": the transform has an entry that is not finite";
+                return VELLO_HIP_E_INVALID;
+            }
+        const FragmentInfo &fi = c->fragments[inst[i].fragment];
+        for (int s = 0; s < 6; s++) len[s] += fi.len[s];
+        n_clips += fi.n_clips;
+        info += fi.info_words;
+        p.brushes = p.brushes || fi.brushes;
+    }
+    // (sums of at most 2^32 terms below 2^32: no u64 overflow)
+    const uint64_t tag_bytes_padded = (len[0] + 1023u) & ~(uint64_t)1023u;
+    const uint64_t total = tag_bytes_padded / 4u + len[1] + len[2] + len[3] + len[4] + len[5];
+    if (total >= ((uint64_t)1 << 32) || tag_bytes_padded >= ((uint64_t)1 << 32) || n_clips > 0xffffffffull || info > 0xffffffffull) {
+        c->last_error = "instances: the composed scene has 2^32 words or more, or a count that leaves u32";
+        return VELLO_HIP_E_INVALID;
+    }
+    for (int s = 0; s < 6; s++) p.len[s] = (uint32_t)len[s];
+    p.tag_words = (uint32_t)(tag_bytes_padded / 4u);
+    vello_hip_layout &L = p.layout;
+    L.n_draw_objects = L.n_paths = p.len[2];
+    L.n_clips = (uint32_t)n_clips;
+    L.bin_data_start = (uint32_t)info;
+    L.path_tag_base = 0u;
+    L.path_data_base = p.tag_words;
+    L.draw_tag_base = L.path_data_base + p.len[1];
+    L.draw_data_base = L.draw_tag_base + p.len[2];
+    L.transform_base = L.draw_data_base + p.len[3];
+    L.style_base = L.transform_base + p.len[4];
+    p.scene_len = (size_t)total * 4u;
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_instances_layout(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, vello_hip_layout *layout_out, size_t *scene_len_out) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    ComposePlan p;
+    if (int r = plan_instances(c, inst, n, p)) return r;
+    if (layout_out) *layout_out = p.layout;
+    if (scene_len_out) *scene_len_out = p.scene_len;
+    return VELLO_HIP_OK;
+}
+
+// vello_hip_render_frame with k_compose_scene in the host copy's place.  Everything that can refuse the frame is asked before the
+// lane is taken; the instance table goes through a pinned block to the lane's own table, on the lane's stream, ahead of the kernel.
+int vello_hip_render_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, const vello_hip_render_params *params, void *out_device,
+                               size_t out_stride) {
+    if (!c || !params) return VELLO_HIP_E_INVALID;
+    ComposePlan p;
+    int r = plan_instances(c, inst, n, p);
+    if (r) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t li = c->next_lane % c->n_active;
+    Lane &l = c->lanes[li];
+    HIP_TRY(c, hipStreamSynchronize(l.stream));
+    // The slot holds no scene until the frame is enqueued: a failure on the way leaves the lane without one, not with a
+    // composed scene whose bytes were never written.
+    l.own.resident = false;
+    if ((r = size_slot(c, l.own, p.layout, p.scene_len))) return r;
+    l.own.brushes = p.brushes;
+    l.own.composed = true;
+    l.own.n_ramps = 0;
+    l.use_own = true;
+    if ((r = alloc_lane_scene(c, l, l.own))) return r;
+    uint32_t xf_base;
+    if (c->has_view && (r = view_base(c, l.own, l, xf_base))) return r;
+    const size_t table_bytes = compose_table_words(n) * 4u;
+    Staging *st = nullptr;
+    if ((r = acquire_staging(c, table_bytes, st))) return r;
+    if ((r = ensure(c, l.compose_table, table_bytes))) return r;
+    Frame f;
+    l.own.resident = true;  // (prepare_frame asks for it)
+    // the Config is not sent here (a blocking copy): VELLO_HIP_BUF_CONFIG gets it when it is next read or written
+    if ((r = prepare_frame(c, l, params, out_device, out_stride, f, false))) {
+        l.own.resident = false;
+        return r;
+    }
+    c->cfg_unsent = true;
+    c->next_lane = (li + 1u) % c->n_active;
+    c->last_lane = li;
+    // the table (engine.h ComposeArgs): six exclusive prefixes, the fragment indices, the transforms
+    uint32_t *table = (uint32_t *)st->host;
+    {
+        uint32_t *off[6], run[6] = {};
+        for (int s = 0; s < 6; s++) off[s] = table + (size_t)s * (n + 1u);
+        uint32_t *frag_of = table + 6u * ((size_t)n + 1u);
+        for (uint32_t i = 0; i < n; i++) {
+            const FragmentInfo &fi = c->fragments[inst[i].fragment];
+            for (int s = 0; s < 6; s++) {
+                off[s][i] = run[s];
+                run[s] += fi.len[s];
+            }
+            frag_of[i] = inst[i].fragment;
+            std::memcpy(frag_of + n + (size_t)i * 6u, inst[i].transform, 24);
+        }
+        for (int s = 0; s < 6; s++) off[s][n] = run[s];
+    }
+    ComposeArgs a{};
+    a.lib = (const uint32_t *)c->shared.scene.ptr;
+    a.dst = (uint32_t *)l.own.scene.ptr;
+    a.table = (const uint32_t *)l.compose_table.ptr;
+    a.frags = (const uint32_t *)c->frag_table.ptr;
+    a.n = n;
+    const vello_hip_layout &S = c->shared.layout, &D = p.layout;
+    const uint32_t src_base[6] = {S.path_tag_base, S.path_data_base, S.draw_tag_base, S.draw_data_base, S.transform_base, S.style_base};
+    const uint32_t dst_base[6] = {D.path_tag_base, D.path_data_base, D.draw_tag_base, D.draw_data_base, D.transform_base, D.style_base};
+    const uint64_t total = p.scene_len / 4u;
+    uint64_t steps = (total + 256u * COMPOSE_TARGET_WGS - 1u) / (256u * COMPOSE_TARGET_WGS);
+    steps = steps < 1u ? 1u : steps > COMPOSE_MAX_STEPS ? COMPOSE_MAX_STEPS : steps;
+    a.steps = (uint32_t)steps;
+    uint32_t wg = 0u;
+    for (int s = 0; s < 6; s++) {
+        a.src_base[s] = src_base[s];
+        a.dst_base[s] = dst_base[s];
+        a.len[s] = s == 0 ? p.tag_words : p.len[s];
+        a.wg_first[s] = wg;
+        wg += (uint32_t)(((uint64_t)a.len[s] + steps * 256u - 1u) / (steps * 256u));  // (< 2^32 words / 256 in all)
+    }
+    a.wg_first[6] = wg;
+    a.tag_bytes = p.len[0];
+    l.own.resident = false;
+    HIP_TRY(c, hipMemcpyAsync(l.compose_table.ptr, st->host, table_bytes, hipMemcpyHostToDevice, l.stream));
+    HIP_TRY(c, hipEventRecord(st->done, l.stream));
+    st->busy = true;
+    launch_compose_scene(a, l.stream);
+    HIP_TRY(c, hipGetLastError());
+    l.own.resident = true;
     return run_stage_range(c, l, f, 0, VELLO_HIP_STAGE_FINE);
 }
 
@@ -1647,6 +2060,7 @@ int vello_hip_read_buffer(vello_hip_ctx *c, int id, void *dst, size_t offset, si
     HIP_TRY(c, hipSetDevice(c->device));
     int r = sync_all(c);
     if (r) return r;
+    if (id == VELLO_HIP_BUF_CONFIG && (r = send_config(c))) return r;
     HIP_TRY(c, hipMemcpy(dst, (const char *)b->ptr + offset, size, hipMemcpyDeviceToHost));
     return VELLO_HIP_OK;
 }
@@ -1661,6 +2075,7 @@ int vello_hip_write_buffer(vello_hip_ctx *c, int id, const void *src, size_t off
     HIP_TRY(c, hipSetDevice(c->device));
     int r = sync_all(c);
     if (r) return r;
+    if (id == VELLO_HIP_BUF_CONFIG && (r = send_config(c))) return r;
     HIP_TRY(c, hipMemcpy((char *)b->ptr + offset, src, size, hipMemcpyHostToDevice));
     return VELLO_HIP_OK;
 }

@@ -6,7 +6,8 @@ import enum
 
 import numpy as np
 
-from ._lib import load_library, VelloHipError, Capacities, Bump, LayoutStruct, RenderParamsStruct, ImageCopyStruct
+from ._lib import (load_library, VelloHipError, Capacities, Bump, LayoutStruct, RenderParamsStruct, ImageCopyStruct, FragmentStruct,
+                   InstanceStruct)
 from .scene import Color, ImageAlphaType, ImageData, ImageFormat
 
 
@@ -46,6 +47,56 @@ def _view_floats(view):
     if len(coeffs) != 6:
         raise ValueError("a view transform has six coefficients [m0 m1 m2 m3 t0 t1]")
     return (ctypes.c_float * 6)(*[float(v) for v in coeffs])
+
+
+INSTANCE_DTYPE = np.dtype([("fragment", "<u4"), ("transform", "<f4", (6,))])  # vello_hip_instance, 28 bytes
+assert INSTANCE_DTYPE.itemsize == ctypes.sizeof(InstanceStruct)
+FRAGMENT_STREAMS = ("path_tags", "path_data", "draws", "draw_data", "transforms", "styles")
+
+
+def instance_array(instances):
+    """An INSTANCE_DTYPE array of (fragment index, transform) pairs; a transform is an Affine or six floats [m0 m1 m2 m3 t0 t1]."""
+    if isinstance(instances, np.ndarray) and instances.dtype == INSTANCE_DTYPE:
+        return np.ascontiguousarray(instances)
+    out = np.zeros(len(instances), dtype=INSTANCE_DTYPE)
+    for i, (fragment, transform) in enumerate(instances):
+        out[i]["fragment"] = int(fragment)
+        out[i]["transform"] = [float(v) for v in (transform.c if hasattr(transform, "c") else transform)]
+    return out
+
+
+class FragmentLibrary:
+    """A list of Scenes appended into ONE Scene (Scene.append without a transform), resolved once: what Engine.upload_fragments
+    makes resident.  `fragments[i]` holds scene i's half-open range in each of the six streams, taken from the stream sizes before
+    and after its append; `resolved` is the Resolver's result for the whole (its ramps and atlas serve every instance frame)."""
+
+    def __init__(self, scenes, resolver=None):
+        from .scene import Resolver, Scene
+
+        self.scene = Scene()
+        self.fragments = []
+        before = self._sizes()
+        for s in scenes:
+            self.scene.append(s)
+            after = self._sizes()
+            self.fragments.append({k: (before[k], after[k]) for k in FRAGMENT_STREAMS})
+            before = after
+        self.resolved = (resolver or Resolver()).resolve(self.scene)
+        self.packed, self.layout, self.ramps = self.resolved.packed, self.resolved.layout, self.resolved.ramps
+
+    def _sizes(self):
+        lib, h = self.scene._lib, self.scene._h
+        unit = {"path_tags": 1, "path_data": 4, "draws": 4, "draw_data": 4, "transforms": 24, "styles": 8}
+        return {k: lib.vh_scene_stream_bytes(h, i) // unit[k] for i, k in enumerate(FRAGMENT_STREAMS)}
+
+    def upload(self, engine):
+        """Atlas, ramps, packed scene and the fragment table (Engine.upload_resolved with upload_fragments in upload_scene's place)."""
+        r = self.resolved
+        if r.atlas_size:
+            engine.resize_image_atlas(r.atlas_size, r.atlas_size)
+            for x, y, px in r.uploads:
+                engine.write_image(x, y, px)
+        engine.upload_fragments(r.packed, r.layout, self.fragments, r.ramps)
 
 
 class RendererOptions:
@@ -300,6 +351,45 @@ class Engine:
             rp, nr = ramps.ctypes.data, ramps.size // 512
         self._check(self._lib.vello_hip_render_frame(self._h, packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p),
                                                      rp, nr, ptr, stride), "render_frame")
+
+    def upload_fragments(self, packed, layout, fragments, ramps=None):
+        """vello_hip_upload_fragments: upload_scene plus a fragment table.  `fragments` is a sequence of dicts (or objects with
+        these attributes) holding a half-open (begin, end) range per stream: path_tags, path_data, draws, draw_data, transforms,
+        styles -- what FragmentLibrary.fragments holds."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        lay = LayoutStruct(*layout)
+        rp, nr = None, 0
+        if ramps is not None and len(ramps):
+            ramps = np.ascontiguousarray(ramps, dtype=np.uint32)
+            rp, nr = ramps.ctypes.data, ramps.size // 512
+        arr = (FragmentStruct * max(len(fragments), 1))()
+        for i, f in enumerate(fragments):
+            for name, _ in FragmentStruct._fields_:
+                b, e = f[name] if isinstance(f, dict) else getattr(f, name)
+                getattr(arr[i], name)[:] = (int(b), int(e))
+        self._check(self._lib.vello_hip_upload_fragments(self._h, packed.ctypes.data, packed.nbytes, ctypes.byref(lay), rp, nr, arr,
+                                                         len(fragments)), "upload_fragments")
+
+    def instances_layout(self, instances):
+        """vello_hip_instances_layout: (Layout, scene length in bytes) of the scene that `instances` compose from the resident
+        fragments; host only."""
+        inst = instance_array(instances)
+        lay, n = LayoutStruct(), ctypes.c_size_t()
+        self._check(self._lib.vello_hip_instances_layout(self._h, inst.ctypes.data, len(inst), ctypes.byref(lay), ctypes.byref(n)),
+                    "instances_layout")
+        return Layout(*[getattr(lay, k) for k, _ in LayoutStruct._fields_]), int(n.value)
+
+    def render_instances(self, instances, width, height, base_color, aa, out=None):
+        """vello_hip_render_instances: composes this frame's scene on the GPU from `instances` -- (fragment index, transform) pairs
+        or an INSTANCE_DTYPE array -- of the fragments of upload_fragments, and enqueues the frame like render_frame."""
+        inst = instance_array(instances)
+        p = self._params(width, height, base_color, aa)
+        ptr, stride = None, 0
+        if out is not None:
+            ptr, is_dev = _data_ptr(out, width, height)
+            assert is_dev, "render_instances writes to device memory"
+            stride = width * 4
+        self._check(self._lib.vello_hip_render_instances(self._h, inst.ctypes.data, len(inst), ctypes.byref(p), ptr, stride), "render_instances")
 
     def render_resident(self, width, height, base_color, aa, out=None):
         p = self._params(width, height, base_color, aa)
