@@ -106,9 +106,12 @@ __device__ __forceinline__ float cos_cr(float x) {
     sincos_cr(x, s, c);
     return c;
 }
-// Small-argument fast path: for |y / x| <= 2^-6 the truncated Taylor series evaluated in fp64 is accurate to
-// < 2^-57 relative, i.e. it rounds to the same f32 as the full ocml routine (both are "the exact value
-// rounded once" up to ~2^-29 per call) at a fifth of the instructions.
+// Small-argument fast path: for |y / x| <= 2^-6 the Taylor series truncated after r^11 (the next term is < 2^-75
+// relative) and evaluated in plain, non-fused fp64 is accurate to < 2^-51 relative: three roundings of 2^-53 each
+// reach the result whole -- the quotient, 1 + t and the last product -- and everything inside t is scaled by
+// r^2 <= 2^-12.  That is the error class of the full ocml routine (<= 2 ulp), so it rounds to the same f32 except
+// next to an f32 rounding boundary (~2^-28 of arguments), at a fifth of the instructions.  tests/test_math_rules.py
+// holds it to the oracle's (float)atan2 on the host, bound included; tests/test_gpu_math_rules.py on the device.
 __device__ __forceinline__ float atan2_cr(float y, float x) {
     if (x > 0.0f && fabsf(y) <= 0.015625f * x && fabsf(y) < __builtin_inff()) {  // (inf, inf) is pi/4, not inf / inf
         double r = (double)y / (double)x;

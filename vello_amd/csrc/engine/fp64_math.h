@@ -7,7 +7,9 @@
 // one division, degree-11 polynomial -- came to 113 instructions against ocml's 122, so atan2 stays with ocml.)
 //
 // Every step is an IEEE fp64 operation spelled explicitly (fma where written, no contraction elsewhere), so
-// a host (g++) build of this header computes the same bits as gfx950; tests/test_fp64_math.py does exactly that.
+// a host (g++) build of this header computes the same bits as gfx950: tests/test_gpu_math_rules.py compares the fp64
+// bits of the two builds on the device (tests/device_checks/math.hip); tests/test_fp64_math.py and
+// tests/test_math_rules.py hold the host build to libm.
 //
 // The polynomials are the classical minimax sets for sin/cos on [-pi/4, pi/4] (published with Sun's fdlibm,
 // 1993); tests/test_fp64_math.py measures them against libm.
@@ -56,6 +58,9 @@ __device__ __forceinline__ void sincos_medium(double x, double &s, double &c) {
     const double ca = (q & 1) ? sr : cr;
     s = (q & 2) ? -sa : sa;
     c = ((q + 1) & 2) ? -ca : ca;
+    // sin(-0) is -0 (libm, IEEE 754): the reduction cannot keep it, fma(-k, PIO2_1, x) adds +0 to -0 and the polynomial's
+    // r^3 term does the same again.  Every other argument, denormals included, keeps its sign through r.
+    s = x == 0.0 ? x : s;
 }
 
 // x^y for a finite x > 0 that came from an f32 (24 significant bits, any f32 exponent incl. denormals) and an f32-valued
