@@ -153,7 +153,8 @@ void vello_hip_destroy(vello_hip_ctx *ctx);
 
 /* One frame, host buffers in, blocking: upload + render + (optional) copy out.
  * `out_rgba8` receives un-premultiplied RGBA8 rows of `out_stride` bytes (fine.wgsl:1386-1397);
- * it is a device pointer when out_is_device != 0, else host memory.  `ramps` is the gradient
+ * it is a device pointer when out_is_device != 0, else host memory (address, stride and what is written: THE TARGET at
+ * vello_hip_render_resident).  `ramps` is the gradient
  * ramp texture (512 RGBA8 texels per ramp, vello_encoding/src/ramp_cache.rs:12) or NULL.
  * `bump_out` (nullable) receives the bump counters. */
 int vello_hip_render(vello_hip_ctx *ctx, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
@@ -168,7 +169,16 @@ int vello_hip_upload_scene(vello_hip_ctx *ctx, const uint8_t *scene, size_t scen
  * the scene of the last vello_hip_upload_scene: scenes passed to vello_hip_render_frame are private to their frame
  * (VELLO_HIP_E_INVALID if no scene was ever uploaded).  The frame runs on the context's own (non-blocking) stream
  * (vello_hip_get_stream): work of the caller's streams on `out_device` -- clearing it, reading the previous frame -- has
- * to be finished or ordered against that stream by the caller, as with any wgpu texture shared between queues. */
+ * to be finished or ordered against that stream by the caller, as with any wgpu texture shared between queues.
+ *
+ * THE TARGET (every entry point that takes one: vello_hip_render, _render_resident, _render_frame, _render_instances).
+ * Device target: `out_device` and `out_stride` are multiples of 4; out_stride == 0 means width * 4, otherwise
+ * width * 4 <= out_stride < 2^32 (a stride of 2^32 and more is refused, not supported).  Host target of vello_hip_render
+ * (out_is_device == 0): any alignment; out_stride == 0 or out_stride >= width * 4.  The engine writes exactly the bytes
+ * [y * out_stride, y * out_stride + width * 4) of each row y < height, and no other byte: padding between rows, the pixels
+ * beside a sub-rectangle of a larger surface and everything behind the last row keep their contents.  A target that breaks
+ * this is refused with VELLO_HIP_E_INVALID (vello_hip_last_error names the rule) before anything is uploaded or enqueued:
+ * the target is untouched, the resident scene unchanged, and the in-flight rotation stays where it was. */
 int vello_hip_render_resident(vello_hip_ctx *ctx, const vello_hip_render_params *params, void *out_device, size_t out_stride);
 /* Animation form (every frame has its own scene): vello_hip_upload_scene + vello_hip_render_resident in one call
  * that does NOT wait for the frame.  The scene is copied into the private slot of the next in-flight buffer set

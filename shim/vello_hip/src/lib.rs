@@ -141,6 +141,10 @@ impl HipRenderer {
 
     /// `Renderer::render_to_texture` (vello/src/lib.rs:474-515) into a caller-owned linear RGBA8 buffer (host memory, or
     /// device memory of the context's GPU): un-premultiplied, rows of `stride` bytes, origin top-left.
+    /// The target (include/vello_hip.h, at `vello_hip_render_resident`): on the device, `target` and `stride` are multiples of 4
+    /// and `stride` is 0 (= width * 4) or width * 4 <= stride < 2^32; on the host any alignment, `stride` 0 or >= width * 4.
+    /// Exactly the bytes [y * stride, y * stride + width * 4) of each row y < height are written and no other byte; a target
+    /// that breaks this is `Error::Invalid` before anything is uploaded or enqueued.
     pub fn render_to_buffer(&mut self, scene: &Scene, target: *mut c_void, stride: usize, on_device: bool,
                             params: &RenderParams) -> Result<(), Error> {
         // identical to Render::render_encoding_coarse up to the uploads (vello/src/render.rs:135-232).

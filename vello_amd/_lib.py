@@ -22,6 +22,12 @@ def _use_library(path):
     _LIB_PATH_OVERRIDE = path
 
 
+def is_emulated(lib):
+    """True for the SIMT-emulated build of the kernel sources that the CPU tests load through _use_library (tests/simt_emu): device
+    memory is host memory there, so a numpy array may stand for a device target.  Told by an entry point only that build has."""
+    return hasattr(lib, "simt_emu_switch")
+
+
 class Capacities(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("lines", "bin_data", "tiles", "seg_counts", "segments", "blend_spill", "ptcl")]
 

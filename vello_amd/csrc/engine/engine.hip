@@ -595,6 +595,22 @@ int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &ba
     return 0;
 }
 
+// The target contract of include/vello_hip.h (at vello_hip_render_resident).  fine stores dwords at output + y * stride and takes the
+// stride as a u32: a device target that is not 4-aligned, rows that overlap or a stride of 2^32 and more would corrupt silently.
+// Every entry point that takes a target asks before it uploads, rotates or enqueues anything.
+static int check_target(vello_hip_ctx *c, const vello_hip_render_params *p, const void *out, size_t out_stride, bool device) {
+    if (!out || !p) return VELLO_HIP_OK;
+    const uint64_t row = (uint64_t)p->width * 4u;
+    const char *why = nullptr;
+    if (out_stride != 0u && out_stride < row) why = "out_stride is below width * 4";
+    else if (device && (out_stride ? (uint64_t)out_stride : row) > 0xffffffffull) why = "the row stride of a device target must be below 2^32";
+    else if (device && (out_stride & 3u) != 0u) why = "out_stride of a device target is not a multiple of 4";
+    else if (device && (reinterpret_cast<uintptr_t>(out) & 3u) != 0u) why = "the address of a device target is not a multiple of 4";
+    if (!why) return VELLO_HIP_OK;
+    c->last_error = std::string("target refused: ") + why;
+    return VELLO_HIP_E_INVALID;
+}
+
 int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, void *out_device, size_t out_stride, Frame &f,
                   bool upload_cfg) {
     const SceneSlot &sc = slot_of(c, l);
@@ -1277,6 +1293,7 @@ int vello_hip_render_frame(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
                            const vello_hip_render_params *params, const uint32_t *ramps, uint32_t n_ramps, void *out_device,
                            size_t out_stride) {
     if (!c || !params) return VELLO_HIP_E_INVALID;
+    if (int tr = check_target(c, params, out_device, out_stride, true)) return tr;
     HIP_TRY(c, hipSetDevice(c->device));
     uint32_t li = c->next_lane % c->n_active;
     Lane &l = c->lanes[li];
@@ -1468,6 +1485,7 @@ int vello_hip_render_instances(vello_hip_ctx *c, const vello_hip_instance *inst,
     ComposePlan p;
     int r = plan_instances(c, inst, n, p);
     if (r) return r;
+    if ((r = check_target(c, params, out_device, out_stride, true))) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     uint32_t li = c->next_lane % c->n_active;
     Lane &l = c->lanes[li];
@@ -1698,10 +1716,11 @@ int vello_hip_copy_images_device(vello_hip_ctx *c, const vello_hip_image_copy *c
 
 int vello_hip_render_resident(vello_hip_ctx *c, const vello_hip_render_params *params, void *out_device, size_t out_stride) {
     if (!c) return VELLO_HIP_E_INVALID;
+    int r = check_target(c, params, out_device, out_stride, true);
+    if (r) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     uint32_t li = c->next_lane % c->n_active;
     Lane &l = c->lanes[li];
-    int r;
     if (l.use_own) {
         // the lane last rendered a vello_hip_render_frame scene: resident frames always show the scene of
         // vello_hip_upload_scene, whichever lane the rotation has reached
@@ -2015,7 +2034,8 @@ int vello_hip_render(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, c
                      const vello_hip_render_params *params, const uint32_t *ramps, uint32_t n_ramps, void *out_rgba8, size_t out_stride,
                      int out_is_device, vello_hip_bump *bump_out) {
     if (!c || !params) return VELLO_HIP_E_INVALID;
-    int r;
+    int r = check_target(c, params, out_rgba8, out_stride, out_is_device != 0);
+    if (r) return r;
     if (c->auto_grow && (r = presize_pools(c, scene, scene_len, layout, params))) return r;
     r = vello_hip_upload_scene(c, scene, scene_len, layout, ramps, n_ramps);
     if (r) return r;

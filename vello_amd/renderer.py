@@ -6,7 +6,7 @@ import enum
 
 import numpy as np
 
-from ._lib import (load_library, VelloHipError, Capacities, Bump, LayoutStruct, RenderParamsStruct, ImageCopyStruct, FragmentStruct,
+from ._lib import (load_library, is_emulated, VelloHipError, Capacities, Bump, LayoutStruct, RenderParamsStruct, ImageCopyStruct, FragmentStruct,
                    InstanceStruct)
 from .scene import Color, ImageAlphaType, ImageData, ImageFormat
 
@@ -132,6 +132,47 @@ def _data_ptr(texture, width=None, height=None):
     return ptr, is_dev
 
 
+def _target(lib, texture, width, height, device_only=False, stride=None):
+    """(address, row stride in bytes, is_device) of a render target: the first height x width x 4 bytes of a dense uint8 buffer (as
+    _data_ptr takes it), or an [H, W, 4] uint8 array / tensor of at least that size whose texels are RGBA8 words (stride(2) == 1,
+    stride(1) == 4) and whose rows lie stride(0) bytes apart -- a slice of a larger surface works, as for _texture_source.  The
+    engine writes the first width * 4 bytes of the first `height` rows and nothing else (include/vello_hip.h).  A numpy array is a
+    host target; it stands for device memory only in the SIMT-emulated build, so with `device_only` the GPU build refuses it.
+    `stride` (bytes) replaces the geometry read from `texture`, which then only supplies the address: the engine judges it."""
+    width, height = int(width), int(height)
+    is_np = isinstance(texture, np.ndarray)
+    if not is_np:
+        import torch
+
+        if not isinstance(texture, torch.Tensor):
+            raise ValueError("target must be a numpy array or a torch tensor")
+    dtype_ok = texture.dtype == np.uint8 if is_np else str(texture.dtype) == "torch.uint8"
+    if not dtype_ok:
+        raise ValueError("target must hold uint8")
+    ndim = texture.ndim if is_np else texture.dim()
+    strides = tuple(texture.strides) if is_np else tuple(texture.stride())
+    dense = texture.flags["C_CONTIGUOUS"] if is_np else texture.is_contiguous()
+    if stride is not None:
+        ptr, stride = (texture.ctypes.data if is_np else texture.data_ptr()), int(stride)
+        is_dev = False if is_np else bool(texture.is_cuda)
+    elif dense:
+        ptr, is_dev = _data_ptr(texture, width, height)
+        stride = width * 4
+    elif ndim == 3 and texture.shape[2] == 4 and strides[2] == 1 and strides[1] == 4 and (strides[0] >= 0):
+        if texture.shape[0] < height or texture.shape[1] < width:
+            raise ValueError(f"target is {texture.shape[1]}x{texture.shape[0]}, the frame {width}x{height}")
+        ptr = texture.ctypes.data if is_np else texture.data_ptr()
+        stride = int(strides[0])
+        is_dev = False if is_np else bool(texture.is_cuda)
+    else:
+        raise ValueError("target must be dense, or an [H, W, 4] uint8 view with stride(2) == 1 and stride(1) == 4")
+    if device_only and not is_dev:
+        if not (is_np and is_emulated(lib)):
+            raise ValueError("this entry point writes to device memory: the target must be a tensor on the GPU")
+        is_dev = True
+    return ptr, stride, is_dev
+
+
 def _texture_source(source):
     """(address, row stride in bytes, height, width) of an override source: an [H, W, 4] uint8 tensor on the GPU whose texels
     are RGBA8 words (stride(2) == 1, stride(1) == 4; any row stride, so a slice of a larger tensor works).  A numpy array of
@@ -190,8 +231,7 @@ class Renderer:
     def render_to_texture(self, scene, texture, params):
         """Override sources are copied into the atlas in one batch behind the work already enqueued on torch's current stream,
         which then waits for the copy (vello_hip_copy_images_device)."""
-        ptr, is_dev = _data_ptr(texture, params.width, params.height)
-        stride = params.width * 4
+        ptr, stride, is_dev = _target(self._lib, texture, params.width, params.height)
         src_stream = relay = None
         if any(not isinstance(t, np.ndarray) for t in self._overrides.values()):
             import torch
@@ -286,9 +326,14 @@ class Engine:
         self._check(self._lib.vello_hip_resize_image_atlas(self._h, width, height), "resize_image_atlas")
 
     def write_image(self, x, y, pixels):
-        pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+        """vello_hip_write_image of an [H, W, 4] uint8 host array; its row stride is the array's own, so a slice of a larger array
+        is uploaded without a copy (anything else is made dense first)."""
+        pixels = np.asarray(pixels, dtype=np.uint8)
+        if pixels.ndim != 3 or pixels.shape[2] != 4 or pixels.strides[2] != 1 or pixels.strides[1] != 4 or pixels.strides[0] < pixels.shape[1] * 4:
+            pixels = np.ascontiguousarray(pixels)
         h, w = pixels.shape[:2]
-        self._check(self._lib.vello_hip_write_image(self._h, x, y, w, h, pixels.ctypes.data, w * 4), "write_image")
+        self._check(self._lib.vello_hip_write_image(self._h, x, y, w, h, pixels.ctypes.data, pixels.strides[0] if pixels.ndim == 3 else w * 4),
+                    "write_image")
 
     def copy_images_device(self, copies, stream=None):
         """vello_hip_copy_images_device: `copies` are (x, y, width, height, address, row stride in bytes) entries, copied into the
@@ -335,16 +380,14 @@ class Engine:
                 self.copy_images_device(copies)
         self.upload_scene(resolved.packed, resolved.layout, resolved.ramps)
 
-    def render_frame(self, packed, layout, width, height, base_color, aa, out=None, ramps=None):
+    def render_frame(self, packed, layout, width, height, base_color, aa, out=None, ramps=None, out_stride=None):
         """vello_hip_render_frame: upload this frame's scene into the next in-flight slot and enqueue the frame."""
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
         lay = LayoutStruct(*layout)
         p = self._params(width, height, base_color, aa)
         ptr, stride = None, 0
         if out is not None:
-            ptr, is_dev = _data_ptr(out, width, height)
-            assert is_dev, "render_frame writes to device memory"
-            stride = width * 4
+            ptr, stride, _ = _target(self._lib, out, width, height, device_only=True, stride=out_stride)
         rp, nr = None, 0
         if ramps is not None and len(ramps):
             ramps = np.ascontiguousarray(ramps, dtype=np.uint32)
@@ -379,40 +422,47 @@ class Engine:
                     "instances_layout")
         return Layout(*[getattr(lay, k) for k, _ in LayoutStruct._fields_]), int(n.value)
 
-    def render_instances(self, instances, width, height, base_color, aa, out=None):
+    def render_instances(self, instances, width, height, base_color, aa, out=None, out_stride=None):
         """vello_hip_render_instances: composes this frame's scene on the GPU from `instances` -- (fragment index, transform) pairs
         or an INSTANCE_DTYPE array -- of the fragments of upload_fragments, and enqueues the frame like render_frame."""
         inst = instance_array(instances)
         p = self._params(width, height, base_color, aa)
         ptr, stride = None, 0
         if out is not None:
-            ptr, is_dev = _data_ptr(out, width, height)
-            assert is_dev, "render_instances writes to device memory"
-            stride = width * 4
+            ptr, stride, _ = _target(self._lib, out, width, height, device_only=True, stride=out_stride)
         self._check(self._lib.vello_hip_render_instances(self._h, inst.ctypes.data, len(inst), ctypes.byref(p), ptr, stride), "render_instances")
 
-    def render_resident(self, width, height, base_color, aa, out=None):
+    def render_resident(self, width, height, base_color, aa, out=None, out_stride=None):
+        """vello_hip_render_resident.  `out`: a dense uint8 target of height * width * 4 bytes, or an [H, W, 4] view whose rows lie
+        stride(0) bytes apart (_target); `out_stride` (bytes) overrides the stride taken from it."""
         p = self._params(width, height, base_color, aa)
         ptr, stride = None, 0
         if out is not None:
-            ptr, is_dev = _data_ptr(out, width, height)
-            assert is_dev, "render_resident writes to device memory"
-            stride = width * 4
+            ptr, stride, _ = _target(self._lib, out, width, height, device_only=True, stride=out_stride)
         self._check(self._lib.vello_hip_render_resident(self._h, ctypes.byref(p), ptr, stride), "render_resident")
 
-    def render(self, packed, layout, width, height, base_color, aa, ramps=None):
-        """One blocking frame; returns (HxWx4 uint8 image, bump dict)."""
+    def render(self, packed, layout, width, height, base_color, aa, ramps=None, out=None, out_stride=None, out_is_device=None):
+        """One blocking frame; returns (HxWx4 uint8 image, bump dict).  With `out` (a target as render_resident takes it; a host
+        array too) the frame is written there and `out` is returned in the image's place.  `out_stride` overrides the row stride
+        taken from `out` (bytes; a host target may have any stride of at least width * 4, an odd one included: pass a flat uint8
+        buffer); `out_is_device` says that a numpy array stands for device memory (the emulated build only)."""
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
         lay = LayoutStruct(*layout)
         p = self._params(width, height, base_color, aa)
-        out = np.zeros((height, width, 4), dtype=np.uint8)
+        if out is None:
+            out = np.zeros((height, width, 4), dtype=np.uint8)
+        out_ptr, stride, is_dev = _target(self._lib, out, width, height, stride=out_stride)
+        if out_is_device:
+            if not is_dev and not (isinstance(out, np.ndarray) and is_emulated(self._lib)):
+                raise ValueError("out_is_device: the target is not device memory")
+            is_dev = True
         b = Bump()
         rp, nr = None, 0
         if ramps is not None and len(ramps):
             ramps = np.ascontiguousarray(ramps, dtype=np.uint32)
             rp, nr = ramps.ctypes.data, ramps.size // 512
         r = self._lib.vello_hip_render(self._h, packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p), rp, nr,
-                                       out.ctypes.data, width * 4, 0, ctypes.byref(b))
+                                       out_ptr, stride, 1 if is_dev else 0, ctypes.byref(b))
         if r != 0 and r != E_CAPACITY:
             self._check(r, "render")
         return out, b.as_dict()
