@@ -82,7 +82,7 @@ def main():
         wg = "-" if lds == 0 else str(160 * 1024 // lds)
         print(f"{n[:48]:48s} {r['vgpr_count']:>5s} {r.get('agpr_count', '0'):>5s} {r['sgpr_count']:>5s} {r.get('vgpr_spill_count', '0'):>7s} "
               f"{r.get('sgpr_spill_count', '0'):>7s} {r.get('private_segment_fixed_size', '0'):>9s} {lds:>7d} {wps:>10d} {wg:>9s}")
-    print("# (kernels with dynamic LDS -- k_coarse, the flatten kernels -- add what engine.hip passes at launch: DESIGN.md 3.3 / 3.4)")
+    print("# (kernels with dynamic LDS -- k_coarse, the flatten kernels -- add what their launch_* functions pass at launch: DESIGN.md 3.3 / 3.4)")
 
 
 if __name__ == "__main__":

@@ -140,3 +140,20 @@ def test_cpp_example_builds_and_fails_loudly_without_a_gpu(built, tmp_path):
     assert tuple(img[10, 10]) == (26, 26, 31)            # base colour
     assert tuple(img[256, 300]) != tuple(img[256, 200])  # the sweep gradient varies around the centre
     assert tuple(img[256, 66]) == tuple(img[256, 446])   # the stroke-clipped ring, symmetric
+
+
+def test_destroy_frees_every_device_buffer(built, tmp_path):
+    # tests/c_abi/engine_lifecycle.cpp drives every allocator of the host driver once and destroys the context.  Only the program
+    # is built with -fsanitize=address; linked against the emulated kernels, whose hipMalloc is calloc, LeakSanitizer sees any
+    # device buffer or staging block that vello_hip_destroy forgets.  A child process of its own.
+    import subprocess
+
+    exe = str(tmp_path / "engine_lifecycle")
+    src = os.path.join(ROOT, "tests", "c_abi", "engine_lifecycle.cpp")
+    emu = os.path.join(ROOT, "tests", "simt_emu")
+    # (the sanitizer's runtime is linked into the program itself: it is there first whatever else the process loads)
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address", "-static-libasan", src, "-I", ROOT, "-L", emu, "-lvello_emu",
+                    f"-Wl,-rpath,{emu}", "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "Sanitizer" not in r.stderr, r.stderr

@@ -1,0 +1,250 @@
+// The host driver's data model -- the context, its lanes, its scene slots -- and the helpers its translation units share.
+// (engine.h is the interface between the driver and the kernels; this header is the driver's own.)
+#pragma once
+#include "../../../include/vello_hip.h"
+
+#include <string>
+#include <vector>
+
+#include "engine.h"
+
+namespace vk {
+
+// A device allocation, owned by the struct that holds it: freed with it.  (vello_hip_destroy sets the device and waits for every
+// stream before the context and its lanes go away.)
+struct DevBuf {
+    void *ptr = nullptr;
+    size_t size = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : ptr(o.ptr), size(o.size) { o.ptr = nullptr, o.size = 0; }
+    ~DevBuf() {
+        if (ptr) (void)hipFree(ptr);
+    }
+};
+
+inline uint32_t align_up(uint32_t len, uint32_t alignment) { return len + ((0u - len) & (alignment - 1u)); }
+
+// One frame in flight = one lane: its own stream and its own set of transient buffers.  The packed scene,
+// ramps and mask LUTs are shared read-only.  wgpu queues recordings without waiting (wgpu_engine.rs:757); here
+// consecutive frames additionally overlap on the GPU (coarse launches only one workgroup per bin, fine and
+// flatten are latency-bound, so a second frame fills the idle CUs): vello_hip_set_frames_in_flight.
+// A packed scene made resident: the bytes, the ramp texture and everything the host derives from the Layout.
+struct SceneSlot {
+    DevBuf scene, ramps;
+    vello_hip_layout layout{};
+    size_t scene_len = 0;
+    uint32_t n_tag_words = 0, n_pathtag_parts = 0, n_draw_parts = 0, n_ramps = 0;
+    size_t zero_bytes = 0;
+    bool brushes = false;   // gradient / image / blurred-rect draw objects present (selects fine's specialisation)
+    bool resident = false;
+    // stroked-line tags of the scene as k_flatten_light counted them in an earlier frame (-1: not known yet).  A property of
+    // the scene alone; lets the host leave out stroke workgroups that would exit at once.
+    int64_t stroke_lines = -1;
+    // lines in the soup of a finished frame of this scene (-1 unknown): picks path_count's chunk size (path.hip, k_path_count<LPT>)
+    int64_t soup_lines = -1;
+    int64_t slice_demand = -1;  // slice items coarse asked for in a finished MSAA frame of this scene (max seen), -1 unknown
+    // what k_flatten_light put on flatten's heavy list in a finished frame of this scene: fills' curves, stroked curves (+ the cap
+    // markers of open subpaths), stroked lines (-1: not known yet): picks the kernels that take the list (Frame::flatten_coop)
+    int64_t heavy_curves = -1, heavy_strokes = -1;
+    uint64_t generation = 0;  // bumped by every upload into the slot: a lane's finished frame speaks for the scene it rendered only
+    // The composed transform words of frames with a view (vello_hip_set_view_transform, Frame::xf_base): `view_sets` copies of
+    // (n_xf + 1) * 6 words each, from word `view_at` of the scene's allocation -- behind the scene's bytes and their slack, never
+    // part of what VELLO_HIP_BUF_SCENE shows.  The shared slot holds a copy per lane (frames in flight have views of their own), a
+    // lane's private slot one.
+    size_t view_at = 0;
+    size_t view_cap_bytes = 0;  // bytes allocated from view_at on (ensure_scene)
+    uint32_t view_sets = 0, view_set_words = 0;
+    // the bytes were composed from the library's fragments (vello_hip_render_instances): ramps are the shared slot's
+    bool composed = false;
+};
+// A fragment of the library as the host keeps it: where its range begins in each stream and how long it is -- in the units of
+// ComposeArgs (bytes for tags, words otherwise) -- and what the composed layout and fine's specialisation need of its draw tags.
+struct FragmentInfo {
+    uint32_t begin[6], len[6];
+    uint32_t n_clips, info_words;
+    bool brushes;
+};
+constexpr uint32_t MAX_LANES = 8;
+
+struct Lane {
+    hipStream_t stream = nullptr;
+    SceneSlot own;          // vello_hip_render_frame: the scene of the frame this lane is rendering
+    bool use_own = false;   // else the context's shared scene (vello_hip_upload_scene)
+    DevBuf buf[VELLO_HIP_BUF_COUNT];  // SCENE / CONFIG / BUMP entries unused (shared, see ctx; the head of zero_region: find_buf)
+    DevBuf zero_region;               // Control + look-back states
+    DevBuf clip_stack;
+    DevBuf coarse_el;                 // coarse: CoarseEl per draw object
+    DevBuf tile_bits;                 // coarse: 3 bits per tile of the pool, a word per 8 tiles
+    DevBuf tile_order;                // coarse -> fine: tiles bucketed by command-list length
+    DevBuf slice_items, slice_counters, cov;  // coarse -> fine: slices of long tiles, their arrival counters, coverage scratch
+    DevBuf heavy_list;                // flatten: tag indices for the heavy code, 4 lists (one u32 per tag each, worst case)
+    DevBuf arc_items;                 // flatten: arcs the stroke workgroups leave to the heavy code (64 B per segment, worst case)
+    DevBuf compose_table;             // vello_hip_render_instances: the frame's ComposeArgs::table
+    DevBuf front_sync;                // k_front's grid-barrier counter (zeroed once, when allocated)
+    uint32_t front_sync_value = 0;    // ... and its value once every launch enqueued so far has run
+    struct EvPair {
+        int stage;
+        hipEvent_t a, b;
+        hipEvent_t mid[2];  // behind the stage's first / second kernel when it has more than one (flatten: 3, coarse: 2)
+    };
+    std::vector<EvPair> events;
+    // hands the lane's events back to the context's pool (which vello_hip_destroy destroys)
+    void return_events(std::vector<hipEvent_t> &pool) {
+        for (auto &ev : events)
+            for (hipEvent_t e : {ev.a, ev.b, ev.mid[0], ev.mid[1]})
+                if (e) pool.push_back(e);
+        events.clear();
+    }
+    bool used = false;
+    bool slices_on = false;   // the lane's latest frame ran with fine's slices enabled (an MSAA frame)
+    uint32_t slice_cap_coarse = 0;  // slice blocks the lane's latest COARSE launch was told of (a later FINE must launch as many)
+    uint32_t slice_fills_coarse = 0;  // ... and the slice size it cut with (0: no slices -- an area-AA frame)
+    bool flatten_ran = false;  // the control block holds flatten's counts (a partial vello_hip_run_stages range may stop before it)
+    uint64_t frame_generation = 0;  // slot_of(...).generation when the lane's latest frame was set up
+    uint64_t atlas_epoch_seen = 0;  // ctx::atlas_epoch the lane's stream has been ordered behind
+};
+
+// Pinned staging block of one vello_hip_write_image: the caller's pixels are copied here during the call, the DMA into the
+// atlas runs from it on the upload stream; free again once `done` has passed.
+struct Staging {
+    void *host = nullptr;
+    size_t size = 0;
+    hipEvent_t done = nullptr;
+    bool busy = false;
+    Staging() = default;
+    Staging(Staging &&o) noexcept : host(o.host), size(o.size), done(o.done), busy(o.busy) { o.host = nullptr, o.done = nullptr; }
+    ~Staging() {
+        if (host) (void)hipHostFree(host);
+        if (done) (void)hipEventDestroy(done);
+    }
+};
+
+}  // namespace vk
+
+struct vello_hip_ctx {
+    int device = 0;
+    uint32_t aa_mask = 0;
+    vello_hip_capacities caps{};
+    vk::DevBuf config;
+    vk::DevBuf mask8, mask16;
+    vk::SceneSlot shared;  // vello_hip_upload_scene: one scene for every lane
+    // vello_hip_upload_fragments: the shared scene as a library of fragments (dropped by the next vello_hip_upload_scene)
+    std::vector<vk::FragmentInfo> fragments;
+    bool have_fragments = false;
+    vk::DevBuf frag_table;  // ComposeArgs::frags
+    vk::DevBuf atlas;  // persistent image atlas (render.rs:160-176), shared by all lanes
+    uint32_t atlas_w = 0, atlas_h = 0;
+    std::vector<vk::Lane> lanes;
+    uint32_t n_active = 1;  // lanes in the rotation (<= lanes.size(): shrinking keeps the buffers)
+    uint32_t next_lane = 0, last_lane = 0;
+    bool auto_grow = false;
+    bool viewport_cull = false;  // vello_hip_set_viewport_cull: copied into every Frame when it is prepared
+    bool has_view = false;       // vello_hip_set_view_transform: likewise
+    vk::Xform view{1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
+    hipStream_t copy_stream = nullptr;  // vello_hip_gather_frames: this context's peer copy
+    hipEvent_t frame_done = nullptr;
+    // vello_hip_write_image: atlas uploads are stream-ordered, not host-synchronous (wgpu's queue.write_texture is queued
+    // too, render.rs:160-203).  An upload waits for the frames enqueued before it (they may sample the texels it replaces)
+    // and every frame enqueued after it waits for `atlas_ready`.
+    hipStream_t upload_stream = nullptr;
+    hipEvent_t atlas_ready = nullptr, lane_mark = nullptr;
+    uint64_t atlas_epoch = 0;  // uploads enqueued so far
+    std::vector<vk::Staging> staging;
+    vk::DevBuf copy_descs;  // vello_hip_copy_images_device: the batch's AtlasCopyDesc table (written and read on the upload stream only)
+    uint32_t debug_flags = 0;  // VELLO_HIP_DEBUG_*
+    bool force_brushes = false;  // pre-warm: run fine's brush specialisation on a scene without brushes
+    uint32_t last_render_attempts = 0;  // rounds the last vello_hip_render needed (robust mode)
+    uint64_t fused_launches = 0;  // k_front launches so far (vello_hip_fused_launches)
+    uint64_t scene_allocations = 0;  // scene buffers allocated so far (vello_hip_scene_allocations)
+    // last frame
+    vk::Config cfg{};
+    bool have_cfg = false;
+    bool cfg_unsent = false;  // `cfg` is newer than the device copy (vello_hip_render_instances): sent when VELLO_HIP_BUF_CONFIG is next touched
+    // profiling
+    uint32_t prof_mask = 0;
+    std::vector<hipEvent_t> event_pool;
+    float stage_ms[VELLO_HIP_STAGE_COUNT] = {};
+    uint32_t stage_count[VELLO_HIP_STAGE_COUNT] = {};
+    float kernel_ms[VELLO_HIP_STAGE_COUNT][3] = {};  // per kernel of the stages that are several (flatten, coarse)
+    uint32_t kernel_count[VELLO_HIP_STAGE_COUNT] = {};
+    std::string last_error;
+};
+
+namespace vk {
+
+#define HIP_TRY(ctx, expr)                                                                             \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) {                                                                        \
+            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);                     \
+            return VELLO_HIP_E_HIP;                                                                    \
+        }                                                                                              \
+    } while (0)
+
+inline SceneSlot &slot_of(vello_hip_ctx *c, Lane &l) { return l.use_own ? l.own : c->shared; }
+// bytes between the rows of a target
+inline size_t row_stride(const vello_hip_render_params *p, size_t out_stride) { return out_stride ? out_stride : (size_t)p->width * 4u; }
+
+// context.hip
+int ensure(vello_hip_ctx *c, DevBuf &b, size_t bytes);
+int sync_all(vello_hip_ctx *c);
+uint32_t cov_cap_words(const vello_hip_capacities &d, uint32_t aa_mask);
+int commit_caps(vello_hip_ctx *c, const vello_hip_capacities &d);
+int presize_pools(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout, const vello_hip_render_params *params);
+int alloc_lane_scene(vello_hip_ctx *c, Lane &l, const SceneSlot &sc);
+// frames.hip
+int check_target(vello_hip_ctx *c, const vello_hip_render_params *p, const void *out, size_t out_stride, bool device);
+int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
+int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, void *out_device, size_t out_stride, Frame &f, bool upload_cfg);
+int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int last);
+// scenes.hip
+int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+              const uint32_t *ramps, uint32_t n_ramps);
+// atlas.hip
+int acquire_staging(vello_hip_ctx *c, size_t bytes, Staging *&out);
+// seams.hip
+hipEvent_t get_event(vello_hip_ctx *c);
+
+// One step of enter_frame that an entry point has nothing to add to.
+constexpr auto no_step = [](Lane &) { return 0; };
+
+// How vello_hip_render_frame, vello_hip_render_instances and vello_hip_render_resident enqueue a frame on the next lane of the
+// rotation; each hands in what it does differently:
+//   set_up(l, new_scene)   waits for the lane where it must and gives it its scene slot (l.use_own); new_scene = false where the
+//                          lane's scene-dependent buffers already fit the slot
+//   rotate_first           the rotation moves before prepare_frame (a frame that prepare_frame refuses has then moved it) or only
+//                          once prepare_frame has accepted the frame
+//   staged(l)              what else may refuse the frame, asked after the view's pre-check and before prepare_frame
+//   enqueue(l)             what the lane's stream gets ahead of the stages
+// The view's pre-check (view_base) comes before the rotation moves, for the slot the frame will read -- not for a shared slot that
+// holds no scene: prepare_frame refuses that frame itself.  A composed slot whose frame prepare_frame refuses holds no scene: its
+// bytes were never written.
+template <class SetUp, class Staged, class Enqueue>
+int enter_frame(vello_hip_ctx *c, const vello_hip_render_params *params, void *out_device, size_t out_stride, bool rotate_first, int last,
+                SetUp set_up, Staged staged, Enqueue enqueue) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t li = c->next_lane % c->n_active;
+    Lane &l = c->lanes[li];
+    int r;
+    bool new_scene = true;
+    if ((r = set_up(l, new_scene))) return r;
+    if (new_scene && (r = alloc_lane_scene(c, l, slot_of(c, l)))) return r;
+    uint32_t xf_base;
+    if (c->has_view && (l.use_own || c->shared.resident) && (r = view_base(c, slot_of(c, l), l, xf_base))) return r;
+    if ((r = staged(l))) return r;
+    const auto rotate = [&] {
+        c->next_lane = (li + 1u) % c->n_active;
+        c->last_lane = li;
+    };
+    if (rotate_first) rotate();
+    Frame f;
+    if ((r = prepare_frame(c, l, params, out_device, out_stride, f, false))) {
+        if (slot_of(c, l).composed) slot_of(c, l).resident = false;
+        return r;
+    }
+    if (!rotate_first) rotate();
+    if ((r = enqueue(l))) return r;
+    return run_stage_range(c, l, f, 0, last);
+}
+
+}  // namespace vk

@@ -1,4 +1,4 @@
-// Engine-internal interface between the host driver (engine.hip) and the kernel translation units.
+// Engine-internal interface between the host driver (ctx.h and the sources that include it) and the kernel translation units.
 #pragma once
 #include <cstddef>
 #include "common.h"
@@ -208,7 +208,7 @@ inline Config xf_config(const Frame &f) {
     c.layout.transform_base = f.xf_base;
     return c;
 }
-// k_view_transforms (engine.hip): fills the frame's composed transform words; launched at the head of a frame that has a view
+// k_view_transforms (scene_ops.hip): fills the frame's composed transform words; launched at the head of a frame that has a view
 void launch_view_transforms(const Frame &f, hipStream_t s);
 
 void launch_pathtag_scan(const Frame &f, hipStream_t s);
@@ -226,11 +226,14 @@ constexpr uint32_t FRONT_ZERO = 1u, FRONT_PATHTAG = 2u, FRONT_LIGHT = 4u, FRONT_
 constexpr uint32_t FRONT_MAX_TAGS = 16384u, FRONT_MAX_DRAW_OBJECTS = 4096u;
 constexpr uint32_t FRONT_TINY_SEGMENTS = 64u;  // up to here the heavy list joins the launch, which is then ONE workgroup
 uint32_t launch_front(const Frame &f, hipStream_t s, uint32_t stages, bool with_draw_scan, uint32_t sync_base);
-inline uint32_t flatten_n_seg_max(const Frame &f) {
+// The most segments a scene of this layout (Layout or vello_hip_layout) and tag-word count can hold
+template <class L>
+inline uint32_t flatten_n_seg_max(const L &layout, uint32_t n_tag_words) {
     // (a segment owns at least one word of path data, so the path-data stream bounds the segments even though the tag stream is padded)
-    const uint32_t n_tags = f.n_tag_words * 4u, n_data = f.cfg.layout.draw_tag_base - f.cfg.layout.path_data_base;
-    return n_tags < n_data ? n_tags : n_data;
+    const uint64_t n_tags = (uint64_t)n_tag_words * 4u, n_data = layout.draw_tag_base - layout.path_data_base;
+    return (uint32_t)(n_tags < n_data ? n_tags : n_data);
 }
+inline uint32_t flatten_n_seg_max(const Frame &f) { return flatten_n_seg_max(f.cfg.layout, f.n_tag_words); }
 void launch_draw_scan(const Frame &f, hipStream_t s);
 void launch_clip(const Frame &f, hipStream_t s);             // clip.hip
 void launch_clip_sequential(const Frame &f, hipStream_t s);  // draw.hip
@@ -244,7 +247,7 @@ int enable_coarse_lds();  // hipError_t of the per-device dynamic-LDS opt-in
 void launch_path_tiling(const Frame &f, hipStream_t s);
 void launch_fine(const Frame &f, hipStream_t s);
 
-// Device-to-atlas copies (vello_hip_copy_images_device, engine.hip): one rectangle of raw RGBA8 words per entry.  `first` is
+// Device-to-atlas copies (vello_hip_copy_images_device, atlas.hip; k_atlas_copy, scene_ops.hip): one rectangle of raw RGBA8 words per entry.  `first` is
 // the exclusive prefix of width * height over the batch, so the batch is one concatenated texel space that k_atlas_copy
 // cuts into equal chunks whatever the rectangles' sizes.  Zero-sized rectangles are left out of the table by the host.
 struct AtlasCopyDesc {
@@ -258,7 +261,7 @@ static_assert(sizeof(AtlasCopyDesc) == 40, "AtlasCopyDesc");
 // `descs`: n entries in device memory, `total` = the last entry's first + its texels (> 0)
 void launch_atlas_copy(const AtlasCopyDesc *descs, uint32_t n, uint64_t total, uint32_t *atlas, uint32_t atlas_w, hipStream_t s);
 
-// Scene instances (vello_hip_render_instances, engine.hip): what k_compose_scene is handed by value.  Streams are numbered in the order
+// Scene instances (vello_hip_render_instances, scenes.hip; k_compose_scene, scene_ops.hip): what k_compose_scene is handed by value.  Streams are numbered in the order
 // the packed scene holds them: 0 path tags, 1 path data, 2 draw tags, 3 draw data, 4 transforms, 5 styles.  Every offset is in u32 words
 // but the tag stream's, which are in bytes.
 //   table: [6][n + 1] exclusive prefixes of the instances' lengths per stream -- one stream's offsets are consecutive words, so a

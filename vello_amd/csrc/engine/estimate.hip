@@ -255,7 +255,7 @@ extern "C" int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t s
                 float t[6];
                 std::memcpy(t, &w[L.transform_base + n_xf_seen * 6u], sizeof t);
                 if (view) {
-                    // V.T in f32, as k_view_transforms (engine.hip) and Transform::mul (math.rs:51-73) compute it: the estimator sees
+                    // V.T in f32, as k_view_transforms (scene_ops.hip) and Transform::mul (math.rs:51-73) compute it: the estimator sees
                     // the transform words the frame's kernels read
                     const float *v = view;
                     const float c[6] = {v[0] * t[0] + v[2] * t[1], v[1] * t[0] + v[3] * t[1], v[0] * t[2] + v[2] * t[3], v[1] * t[2] + v[3] * t[3],

@@ -1631,7 +1631,7 @@ __device__ __forceinline__ void heavy_workgroups(FlattenShared<FLATTEN_LDS_LINES
                      : e3 < n_handed  ? heavy_list[3u * n_tags + e3]
                                       : heavy_list[2u * n_tags + e2];
         }
-        // (COOP is the host's choice for the scene, engine.hip Frame::flatten_coop: the kernels of the cooperative walk, with the fp64
+        // (COOP is the host's choice for the scene, prepare_frame in frames.hip, Frame::flatten_coop: the kernels of the cooperative walk, with the fp64
         // routines out of line, or round 4's, every lane on its own with the routines inline -- flatten_walk.inc's head says why)
         uint32_t tag_key = 0u;
         if (COOP) tag_key = flatten_tag_coop(em, coop[tid >> 6], has_tag, cfg, scene, tag_monoids, tag_ix, lane, lpw <= 4u);

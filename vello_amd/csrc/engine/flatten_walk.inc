@@ -13,7 +13,7 @@
 // (k_flatten_main on the road map 64 -> 71 us, mmark-50k 267 -> 321).  Both flavours in ONE kernel spill everywhere (94 us), the
 // cooperative walk as an out-of-line function with a register allocation of its own makes the kernel spill its state around the
 // call (120 us).  Registers are allocated per KERNEL: so two sets of kernels, and the host launches the set the scene's heavy list
-// asks for (engine.hip: Frame::flatten_coop).
+// asks for (prepare_frame in frames.hip: Frame::flatten_coop).
 // Not a header: no include guard, nothing declared beyond what it defines.
 // flatten.wgsl:94-133
 // (out of line as a WHOLE, its two atan2 and two sincos inline inside it: one call a turn instead of four -- see fl_sincos_call)

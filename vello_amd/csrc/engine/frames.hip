@@ -1,0 +1,578 @@
+// Frames: from render parameters to the launch sequence of one frame on one lane, and the entry points that render and wait.
+#include <cstdio>
+#include <cstring>
+
+#include "ctx.h"
+
+using namespace vk;
+
+namespace {
+
+// RenderConfig::new + BufferSizes::new, vello_encoding/src/config.rs:168-196, :363-435
+int configure(vello_hip_ctx *c, const SceneSlot &sc, const vello_hip_render_params *p, Config &cfg) {
+    if (!p || p->width == 0 || p->height == 0 || p->aa > VELLO_HIP_AA_MSAA16) {
+        c->last_error = "invalid render params";
+        return VELLO_HIP_E_INVALID;
+    }
+    if (((c->aa_mask >> p->aa) & 1u) == 0u) {
+        // render.rs:566-568, :593-598: "shaders not configured to support AA mode"
+        c->last_error = "AA mode was not enabled in vello_hip_create(aa_mask)";
+        return VELLO_HIP_E_INVALID;
+    }
+    if (p->width > 0xffffu * TILE_WIDTH || p->height > 0xffffu * TILE_HEIGHT) {
+        c->last_error = "target larger than 65535 tiles in one dimension";  // coarse packs tile coordinates in 16 bits
+        return VELLO_HIP_E_INVALID;
+    }
+    std::memset(&cfg, 0, sizeof cfg);
+    cfg.width_in_tiles = align_up(p->width, TILE_WIDTH) / TILE_WIDTH;
+    cfg.height_in_tiles = align_up(p->height, TILE_HEIGHT) / TILE_HEIGHT;
+    cfg.target_width = p->width;
+    cfg.target_height = p->height;
+    cfg.base_color = p->base_color;
+    std::memcpy(&cfg.layout, &sc.layout, sizeof(Layout));
+    uint32_t bin_data = c->caps.bin_data;
+    if (bin_data <= sc.layout.bin_data_start) {
+        c->last_error = "bin_data capacity smaller than the scene's info words";
+        return VELLO_HIP_E_INVALID;
+    }
+    cfg.lines_size = c->caps.lines;
+    cfg.binning_size = bin_data - sc.layout.bin_data_start;
+    cfg.tiles_size = c->caps.tiles;
+    cfg.seg_counts_size = c->caps.seg_counts;
+    cfg.segments_size = c->caps.segments;
+    cfg.blend_size = c->caps.blend_spill;
+    cfg.ptcl_size = c->caps.ptcl;
+    uint64_t initial_ptcl = (uint64_t)cfg.width_in_tiles * cfg.height_in_tiles * PTCL_INITIAL_ALLOC;
+    if (initial_ptcl + PTCL_INCREMENT > cfg.ptcl_size) {
+        c->last_error = "ptcl capacity smaller than the fixed per-tile allocation";
+        return VELLO_HIP_E_INVALID;
+    }
+    return 0;
+}
+
+// k_front's grid-barrier counter (Lane::front_sync) only ever grows, and the host keeps its value: a launch's barriers wait for
+// sync_base + k * (its workgroups).  The two must never drift apart: if a launch is rejected the device never adds, if a
+// barrier's spin bound trips the workgroups stop waiting -- either way the counter goes back to zero on the lane's stream, behind
+// whatever was enqueued, and the host's copy with it.
+void reset_front_sync(Lane &l, hipStream_t st) {
+    if (l.front_sync.ptr) (void)hipMemsetAsync(l.front_sync.ptr, 0, 256, st);
+    l.front_sync_value = 0u;
+}
+// After a k_front launch: the host's copy of the counter advances only once the launch was accepted.
+int front_accepted(vello_hip_ctx *c, Lane &l, hipStream_t st, uint32_t add) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        reset_front_sync(l, st);
+        c->last_error = std::string("k_front launch: ") + hipGetErrorString(e);
+        return VELLO_HIP_E_HIP;
+    }
+    l.front_sync_value += add;
+    c->fused_launches++;
+    return 0;
+}
+
+// What a finished frame (one that did not fail, and whose flatten ran to its end) teaches about the scene it rendered
+void learn_from_frame(SceneSlot &sc, const Control &ctl, const Lane &l) {
+    sc.stroke_lines = (int64_t)ctl.heavy_count[2];
+    sc.heavy_curves = (int64_t)ctl.heavy_count[0];
+    sc.heavy_strokes = (int64_t)ctl.heavy_count[1];
+    sc.soup_lines = (int64_t)ctl.bump.lines;
+    if (l.slices_on && (int64_t)ctl.slice_items > sc.slice_demand) sc.slice_demand = (int64_t)ctl.slice_items;
+}
+
+// bump.failed of ONE lane's latest frame -> error code.  Failures are per frame: vello_hip_render judges the lane that
+// rendered its frame, vello_hip_sync the lanes of the current rotation, and vello_hip_grow_pools voids the frames that
+// overflowed the old pools (l.used) -- so a retry on another lane is not failed by the lane that overflowed.
+int check_lane(vello_hip_ctx *c, Lane &l) {
+    if (!l.used || !l.zero_region.ptr) return VELLO_HIP_OK;
+    Control ctl;
+    HIP_TRY(c, hipMemcpy(&ctl, l.zero_region.ptr, sizeof ctl, hipMemcpyDeviceToHost));
+    vello_hip_bump b;
+    std::memcpy(&b, &ctl.bump, sizeof b);
+    if (b.failed == 0u) {
+        SceneSlot &sc = slot_of(c, l);
+        if (l.flatten_ran && l.frame_generation == sc.generation) learn_from_frame(sc, ctl, l);  // (flatten ran to its end)
+        return VELLO_HIP_OK;
+    }
+    if ((b.failed & FAILED_SCENE) != 0u) {
+        c->last_error = "the path tag stream needs more path data, transforms or styles than the scene buffer holds";
+        return VELLO_HIP_E_INVALID;
+    }
+    if ((b.failed & FAILED_INTERNAL) != 0u) {
+        // a spin bound tripped (lookback.h, k_front's barrier): not a pool overflow -- growing pools would not help.  The lane is idle
+        // here (the caller waited for it): its barrier counter starts over.
+        reset_front_sync(l, l.stream);
+        (void)hipStreamSynchronize(l.stream);
+        c->last_error = "an engine-internal wait gave up (bump.failed bit 31): the frame is discarded";
+        return VELLO_HIP_E_INTERNAL;
+    }
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "bump.failed=0x%x (lines %u, binning %u, tile %u, seg_counts %u, segments %u, ptcl %u)", b.failed,
+                  b.lines, b.binning, b.tile, b.seg_counts, b.segments, b.ptcl);
+    c->last_error = msg;
+    return VELLO_HIP_E_CAPACITY;
+}
+
+}  // namespace
+
+namespace vk {
+
+// Where entry 0 of lane l's copy of the transform words lies, in words from the scene's start (SceneSlot::view_at; six words into
+// the copy: slot -1 comes first).  VELLO_HIP_E_INVALID for a scene so large that the copy is out of a u32 offset's reach.  The entry
+// points that rotate the lanes ask before they rotate, so that a refused frame leaves the rotation where it was.
+int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base) {
+    const size_t set = l.use_own ? 0u : (size_t)(&l - c->lanes.data());
+    const uint64_t at = (uint64_t)sc.view_at + (uint64_t)set * sc.view_set_words + 6u;
+    if (set >= sc.view_sets || at + sc.view_set_words > 0xffffffffull) {
+        c->last_error = "the scene is too large for a view transform (its transform words must lie within 2^32 words of its start)";
+        return VELLO_HIP_E_INVALID;
+    }
+    base = (uint32_t)at;
+    return 0;
+}
+
+// The target contract of include/vello_hip.h (at vello_hip_render_resident).  fine stores dwords at output + y * stride and takes the
+// stride as a u32: a device target that is not 4-aligned, rows that overlap or a stride of 2^32 and more would corrupt silently.
+// Every entry point that takes a target asks before it uploads, rotates or enqueues anything.
+int check_target(vello_hip_ctx *c, const vello_hip_render_params *p, const void *out, size_t out_stride, bool device) {
+    if (!out || !p) return VELLO_HIP_OK;
+    const uint64_t row = (uint64_t)p->width * 4u;
+    const char *why = nullptr;
+    if (out_stride != 0u && out_stride < row) why = "out_stride is below width * 4";
+    else if (device && (uint64_t)row_stride(p, out_stride) > 0xffffffffull) why = "the row stride of a device target must be below 2^32";
+    else if (device && (out_stride & 3u) != 0u) why = "out_stride of a device target is not a multiple of 4";
+    else if (device && (reinterpret_cast<uintptr_t>(out) & 3u) != 0u) why = "the address of a device target is not a multiple of 4";
+    if (!why) return VELLO_HIP_OK;
+    c->last_error = std::string("target refused: ") + why;
+    return VELLO_HIP_E_INVALID;
+}
+
+int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, void *out_device, size_t out_stride, Frame &f,
+                  bool upload_cfg) {
+    const SceneSlot &sc = slot_of(c, l);
+    if (!sc.resident) {
+        c->last_error = "no scene uploaded";
+        return VELLO_HIP_E_INVALID;
+    }
+    int r;
+    if (c->auto_grow && p && p->width && p->height) {
+        // robust mode: a target with more tiles than the PTCL pool's fixed 64 words per tile (config.rs:408 sizes it for
+        // ~1 Mpx) grows the pool instead of failing; the info words of the scene likewise must fit bin_data
+        uint64_t tiles_xy = (uint64_t)(align_up(p->width, TILE_WIDTH) / TILE_WIDTH) * (align_up(p->height, TILE_HEIGHT) / TILE_HEIGHT);
+        uint64_t need_ptcl = tiles_xy * PTCL_INITIAL_ALLOC + 64u * PTCL_INCREMENT;
+        uint64_t need_bin = (uint64_t)sc.layout.bin_data_start + (1u << 16);
+        if (need_ptcl > c->caps.ptcl || need_bin > c->caps.bin_data) {
+            if (need_ptcl > 0xffff0000ull || need_bin > 0xffff0000ull) {
+                c->last_error = "target / scene too large for 32-bit pool offsets";
+                return VELLO_HIP_E_INVALID;
+            }
+            if ((r = sync_all(c))) return r;
+            vello_hip_capacities d = c->caps;
+            if (need_ptcl > d.ptcl) d.ptcl = (uint32_t)(need_ptcl + need_ptcl / 4u);
+            if (need_bin > d.bin_data) d.bin_data = (uint32_t)(need_bin + need_bin / 4u);
+            if ((r = commit_caps(c, d))) return r;
+        }
+    }
+    r = configure(c, sc, p, f.cfg);
+    if (r) return r;
+    c->cfg = f.cfg;
+    c->have_cfg = true;
+    // size-dependent buffers
+    uint32_t wb = (f.cfg.width_in_tiles + 15u) / 16u, hb = (f.cfg.height_in_tiles + 15u) / 16u;
+    uint32_t aligned_n_bins = align_up(wb * hb, 256u);
+    uint32_t binning_wgs = (sc.layout.n_draw_objects + 255u) / 256u;
+    if ((r = ensure(c, l.buf[VELLO_HIP_BUF_BIN_HEADERS], (size_t)(binning_wgs * aligned_n_bins + 1u) * sizeof(BinHeader)))) return r;
+    if (!out_device && (r = ensure(c, l.buf[VELLO_HIP_BUF_OUTPUT], (size_t)p->width * p->height * 4u))) return r;
+    if ((r = ensure(c, l.tile_order, (size_t)f.cfg.width_in_tiles * f.cfg.height_in_tiles * FINE_WORK_BUCKETS * 4u))) return r;
+    // fine launches one (at once exiting) workgroup per slice item it MIGHT be given in front of the tiles' workgroups:
+    // as many as the scene asked for in an earlier frame (+ 1/8), a quarter of the tiles while that is unknown.  Coarse
+    // cuts a tile into slices only if its items fit (the rest are rendered unsliced), so any number is correct.
+    const uint32_t n_tiles_target = f.cfg.width_in_tiles * f.cfg.height_in_tiles;
+    if ((r = ensure(c, l.slice_items, (size_t)n_tiles_target * sizeof(SliceItem)))) return r;
+    if ((r = ensure(c, l.slice_counters, (size_t)n_tiles_target * 4u))) return r;
+    {
+        uint64_t want = sc.slice_demand < 0 ? n_tiles_target / 4u : (uint64_t)sc.slice_demand + (uint64_t)sc.slice_demand / 8u + 16u;
+        if (want < 64u) want = 64u;
+        f.slice_cap = want > n_tiles_target ? n_tiles_target : (uint32_t)want;
+    }
+    // kernels take the ConfigUniform by value (kernarg); the device copy only serves the test seam
+    if (upload_cfg) {
+        HIP_TRY(c, hipMemcpy(c->config.ptr, &f.cfg, sizeof(Config), hipMemcpyHostToDevice));
+        c->cfg_unsent = false;
+    }
+    f.n_tag_words = sc.n_tag_words;
+    f.n_scene_words = (uint32_t)(sc.scene_len / 4u);
+    f.aa = p->aa;
+    f.scene = (const uint32_t *)sc.scene.ptr;
+    f.has_view = c->has_view;
+    f.view = c->view;
+    f.xf_base = sc.layout.transform_base;
+    if (f.has_view && (r = view_base(c, sc, l, f.xf_base))) return r;
+    f.control = (Control *)l.zero_region.ptr;
+    f.zero_bytes = (uint32_t)sc.zero_bytes;
+    f.front_sync = (uint32_t *)l.front_sync.ptr;
+    f.pathtag_state = (unsigned long long *)((char *)l.zero_region.ptr + sizeof(Control));
+    f.draw_state = f.pathtag_state + (size_t)sc.n_pathtag_parts * 10u;
+    f.tag_monoids = (TagMonoid *)l.buf[VELLO_HIP_BUF_TAG_MONOIDS].ptr;
+    f.path_bboxes = (PathBbox *)l.buf[VELLO_HIP_BUF_PATH_BBOXES].ptr;
+    f.lines = (LineSoup *)l.buf[VELLO_HIP_BUF_LINES].ptr;
+    f.draw_monoids = (DrawMonoid *)l.buf[VELLO_HIP_BUF_DRAW_MONOIDS].ptr;
+    f.info_bin_data = (uint32_t *)l.buf[VELLO_HIP_BUF_INFO_BIN_DATA].ptr;
+    f.clip_inp = (Clip *)l.buf[VELLO_HIP_BUF_CLIP_INP].ptr;
+    f.clip_bboxes = (Bbox4 *)l.buf[VELLO_HIP_BUF_CLIP_BBOXES].ptr;
+    f.draw_bboxes = (Bbox4 *)l.buf[VELLO_HIP_BUF_DRAW_BBOXES].ptr;
+    f.bin_headers = (BinHeader *)l.buf[VELLO_HIP_BUF_BIN_HEADERS].ptr;
+    f.paths = (Path *)l.buf[VELLO_HIP_BUF_PATHS].ptr;
+    f.tiles = (Tile *)l.buf[VELLO_HIP_BUF_TILES].ptr;
+    f.seg_counts = (SegmentCount *)l.buf[VELLO_HIP_BUF_SEG_COUNTS].ptr;
+    f.segments = (Segment *)l.buf[VELLO_HIP_BUF_SEGMENTS].ptr;
+    f.ptcl = (uint32_t *)l.buf[VELLO_HIP_BUF_PTCL].ptr;
+    f.blend_spill = (uint32_t *)l.buf[VELLO_HIP_BUF_BLEND_SPILL].ptr;
+    f.clip_stack = (uint32_t *)l.clip_stack.ptr;
+    f.coarse_el = (CoarseEl *)l.coarse_el.ptr;
+    f.tile_bits = (uint32_t *)l.tile_bits.ptr;
+    f.tile_order = (uint32_t *)l.tile_order.ptr;
+    f.slice_items = (SliceItem *)l.slice_items.ptr;
+    f.slice_counters = (uint32_t *)l.slice_counters.ptr;
+    f.cov = (uint32_t *)l.cov.ptr;
+    f.cov_cap = cov_cap_words(c->caps, c->aa_mask);
+    f.slice_fills = f.slice_min_fills = 0u;
+    l.slices_on = p->aa != 0u;
+    if (p->aa != 0u) {
+        const bool forced = (c->debug_flags & VELLO_HIP_DEBUG_FINE_SLICES) != 0u;
+        const bool alone = c->n_active == 1u;
+        f.slice_fills = forced ? FINE_SLICE_FILLS_FORCED : (alone ? FINE_SLICE_FILLS : FINE_SLICE_FILLS_IN_FLIGHT);
+        f.slice_min_fills = forced ? FINE_SLICE_MIN_FILLS_FORCED : (alone ? FINE_SLICE_MIN_FILLS : FINE_SLICE_MIN_FILLS_IN_FLIGHT);
+    }
+    f.heavy_list = (uint32_t *)l.heavy_list.ptr;
+    f.arc_items = (uint32_t *)l.arc_items.ptr;
+    f.output = out_device ? (uint8_t *)out_device : (uint8_t *)l.buf[VELLO_HIP_BUF_OUTPUT].ptr;
+    f.out_stride = row_stride(p, out_device ? out_stride : 0u);
+    const SceneSlot &rs = sc.composed ? c->shared : sc;  // (a composed scene's draw data holds the library's ramp ids)
+    f.ramps = rs.n_ramps ? (const uint32_t *)rs.ramps.ptr : nullptr;
+    f.n_ramps = rs.n_ramps;
+    f.brushes = sc.brushes || c->force_brushes;
+    f.no_cull = (c->debug_flags & VELLO_HIP_DEBUG_NO_CULL) != 0u;
+    f.viewport_cull = c->viewport_cull;
+    f.sequential_clip = (c->debug_flags & VELLO_HIP_DEBUG_SEQ_CLIP) != 0u;
+    f.stroke_kernel_min_lines = (c->debug_flags & VELLO_HIP_DEBUG_STROKE_KERNEL) != 0u ? 0u : FLATTEN_STROKE_KERNEL_MIN_LINES;
+    f.path_count_small = sc.soup_lines >= 0 && sc.soup_lines < PATH_COUNT_SMALL_MAX_LINES;
+    f.flatten_side_by_side = c->n_active == 1u;
+    f.launch_stroke_kernel = sc.stroke_lines < 0 || (uint64_t)sc.stroke_lines >= f.stroke_kernel_min_lines;
+    // Which kernels take flatten's heavy list (flatten_walk.inc).  The wave-cooperative walk pays where a lane alone would loop
+    // long: a list short enough for a wave per entry (<= 4 096: the tiger's 2 300 curves, a circle's four), or one that is mostly
+    // stroked curves (mmark: two offset curves a walk, a dozen lines a turn); the road map's blobs, joins and caps are 10 % faster
+    // with every lane on its own and the fp64 routines inline.  Known from a finished frame of the scene; before there is one, by
+    // the scene's size.
+    {
+        bool coop = flatten_n_seg_max(sc.layout, sc.n_tag_words) <= 16384u;
+        if (sc.heavy_curves >= 0 && sc.stroke_lines >= 0) {
+            const uint64_t nc = (uint64_t)sc.heavy_curves, ns = (uint64_t)sc.heavy_strokes;
+            const uint64_t nl = (uint64_t)sc.stroke_lines < f.stroke_kernel_min_lines ? (uint64_t)sc.stroke_lines : 0u;
+            const uint64_t n_heavy = nc + ns + nl;
+            coop = n_heavy <= 4096u || ns * 2u > n_heavy + nc * 2u;
+        }
+        if (c->debug_flags & VELLO_HIP_DEBUG_FLATTEN_COOP) coop = true;
+        if (c->debug_flags & VELLO_HIP_DEBUG_FLATTEN_ALONE) coop = false;
+        f.flatten_coop = coop;
+    }
+    l.frame_generation = sc.generation;
+    f.atlas = c->atlas_w ? (const uint32_t *)c->atlas.ptr : nullptr;
+    f.atlas_w = c->atlas_w;
+    f.atlas_h = c->atlas_h;
+    f.mask_lut8 = (const uint32_t *)c->mask8.ptr;
+    f.mask_lut16 = (const uint32_t *)c->mask16.ptr;
+    if (l.atlas_epoch_seen != c->atlas_epoch) {  // atlas uploads enqueued since this lane's last frame come first
+        HIP_TRY(c, hipStreamWaitEvent(l.stream, c->atlas_ready, 0));
+        l.atlas_epoch_seen = c->atlas_epoch;
+    }
+    l.used = true;
+    return 0;
+}
+
+int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int last) {
+    hipStream_t st = l.stream;
+    // coarse decides which tiles are cut into slices from the number of slice blocks fine is going to launch: a FINE that
+    // runs in a later call than its COARSE (vello_hip_run_stages) launches with the number COARSE was given, whatever
+    // the scene's demand is known to be by then
+    Frame f = f_in;
+    if (first > VELLO_HIP_STAGE_COARSE) {
+        if (last >= VELLO_HIP_STAGE_FINE && l.slice_fills_coarse != f.slice_fills) {
+            // (coarse's sliced tiles are not in the work buckets: an area-AA fine would never render them)
+            c->last_error = "vello_hip_run_stages: fine's AA mode must be of the same kind (area / MSAA) as the one coarse ran with";
+            return VELLO_HIP_E_INVALID;
+        }
+        f.slice_cap = l.slice_cap_coarse;
+    } else if (last >= VELLO_HIP_STAGE_COARSE) {
+        l.slice_cap_coarse = f.slice_cap;
+        l.slice_fills_coarse = f.slice_fills;
+    }
+    // Small scenes: consecutive stages as one launch (k_front, flatten.hip) -- A: [zero fill | pathtag scan | flatten's light pass
+    // + draw scan], B: [binning | tile_alloc]; a scene of a few dozen segments: everything up to tile_alloc.  Not for a stage that
+    // is being timed on its own.
+    bool fuse_a = false, fuse_b = false, fuse_all = false;
+    // Any scene: binning and tile_alloc as one launch (binning.hip k_binning_tile_alloc) when the range holds both and neither is
+    // timed on its own
+    const bool pair_b = (c->debug_flags & VELLO_HIP_DEBUG_NO_FUSION) == 0u && first <= VELLO_HIP_STAGE_BINNING && last >= VELLO_HIP_STAGE_TILE_ALLOC &&
+                        (c->prof_mask & ((1u << VELLO_HIP_STAGE_BINNING) | (1u << VELLO_HIP_STAGE_TILE_ALLOC))) == 0u;
+    if ((c->debug_flags & VELLO_HIP_DEBUG_NO_FUSION) == 0u && f.n_tag_words * 4u <= FRONT_MAX_TAGS &&
+        f.cfg.layout.n_draw_objects <= FRONT_MAX_DRAW_OBJECTS && f.cfg.layout.n_paths <= FRONT_MAX_DRAW_OBJECTS) {
+        const uint32_t pm = c->prof_mask;
+        const uint32_t mask_a = (1u << VELLO_HIP_STAGE_PATHTAG_SCAN) | (1u << VELLO_HIP_STAGE_FLATTEN) | (1u << VELLO_HIP_STAGE_DRAW_SCAN);
+        const uint32_t mask_b = (1u << VELLO_HIP_STAGE_BINNING) | (1u << VELLO_HIP_STAGE_TILE_ALLOC);
+        fuse_a = first == VELLO_HIP_STAGE_PATHTAG_SCAN && last >= VELLO_HIP_STAGE_FLATTEN && (pm & mask_a) == 0u;
+        fuse_b = first <= VELLO_HIP_STAGE_BINNING && last >= VELLO_HIP_STAGE_TILE_ALLOC && (pm & mask_b) == 0u;
+        // (the heavy list aboard: the kernels of the cooperative walk, no stroke workgroups -- not when a debug flag asks for others)
+        fuse_all = fuse_a && fuse_b && (pm & (1u << VELLO_HIP_STAGE_CLIP)) == 0u && f.cfg.layout.n_clips == 0u &&
+                   flatten_n_seg_max(f) <= FRONT_TINY_SEGMENTS && f.flatten_coop && f.stroke_kernel_min_lines != 0u;
+    }
+    // a frame with a view: its transform words first (outside every stage's events), when the range holds a stage that reads them
+    if (f.has_view && first <= VELLO_HIP_STAGE_DRAW_SCAN && last >= VELLO_HIP_STAGE_FLATTEN) {
+        launch_view_transforms(f, st);
+        HIP_TRY(c, hipGetLastError());
+    }
+    for (int s = first; s <= last; s++) {
+        bool prof = ((c->prof_mask >> s) & 1u) != 0u;
+        uint32_t front_add = 0u;  // what a k_front launch of this stage adds to the lane's barrier counter (0: one workgroup)
+        bool front_launched = false;
+        Lane::EvPair ev{s, nullptr, nullptr, {nullptr, nullptr}};
+        if (prof) {
+            ev.a = get_event(c);
+            ev.b = get_event(c);
+            if (s == VELLO_HIP_STAGE_FLATTEN || s == VELLO_HIP_STAGE_COARSE) ev.mid[0] = get_event(c);
+            if (s == VELLO_HIP_STAGE_FLATTEN) ev.mid[1] = get_event(c);
+            HIP_TRY(c, hipEventRecord(ev.a, st));
+        }
+        switch (s) {
+        case VELLO_HIP_STAGE_PATHTAG_SCAN:
+            // render.rs:313 clears `bump`; the same memset resets both look-back states and tickets
+            l.flatten_ran = false;
+            if (fuse_all) {
+                front_add = launch_front(f, st, FRONT_ZERO | FRONT_PATHTAG | FRONT_LIGHT | FRONT_HEAVY | FRONT_BINNING | FRONT_TILE_ALLOC, true, l.front_sync_value);
+                front_launched = true;
+                break;
+            }
+            if (fuse_a) break;  // (with FLATTEN's first launch)
+            HIP_TRY(c, hipMemsetAsync(l.zero_region.ptr, 0, slot_of(c, l).zero_bytes, st));
+            launch_pathtag_scan(f, st);
+            break;
+        case VELLO_HIP_STAGE_FLATTEN:
+            l.flatten_ran = true;
+            if (fuse_all) break;
+            // (a range that goes on to DRAW_SCAN: that stage's workgroups ride in flatten's first launch)
+            if (fuse_a) {
+                // (k_front's barrier counter advances on the host only once the launch was accepted: ADVICE r5)
+                const uint32_t add = launch_front(f, st, FRONT_ZERO | FRONT_PATHTAG | FRONT_LIGHT, last >= VELLO_HIP_STAGE_DRAW_SCAN, l.front_sync_value);
+                if (int r = front_accepted(c, l, st, add)) return r;
+            }
+            launch_flatten(f, st, prof ? ev.mid : nullptr, last >= VELLO_HIP_STAGE_DRAW_SCAN, fuse_a);
+            break;
+        case VELLO_HIP_STAGE_DRAW_SCAN:
+            if (first > VELLO_HIP_STAGE_FLATTEN) launch_draw_scan(f, st);  // (else: done beside k_flatten_light)
+            break;
+        case VELLO_HIP_STAGE_CLIP: launch_clip(f, st); break;
+        case VELLO_HIP_STAGE_BINNING:
+            if (fuse_all) break;
+            if (fuse_b) {
+                if (f.cfg.layout.n_draw_objects != 0u || f.cfg.layout.n_paths != 0u) {
+                    front_add = launch_front(f, st, FRONT_BINNING | FRONT_TILE_ALLOC, false, l.front_sync_value);
+                    front_launched = true;
+                }
+            } else if (pair_b) {
+                launch_binning_tile_alloc(f, st);
+            } else {
+                launch_binning(f, st);
+            }
+            break;
+        case VELLO_HIP_STAGE_TILE_ALLOC:
+            if (!fuse_all && !fuse_b && !pair_b) launch_tile_alloc(f, st);
+            break;
+        case VELLO_HIP_STAGE_PATH_COUNT: launch_path_count(f, st); break;
+        case VELLO_HIP_STAGE_BACKDROP: launch_backdrop(f, st); break;
+        case VELLO_HIP_STAGE_COARSE: launch_coarse(f, st, prof ? ev.mid : nullptr); break;
+        case VELLO_HIP_STAGE_PATH_TILING: launch_path_tiling(f, st); break;
+        case VELLO_HIP_STAGE_FINE: launch_fine(f, st); break;
+        default: return VELLO_HIP_E_INVALID;
+        }
+        if (front_launched) {
+            if (int r = front_accepted(c, l, st, front_add)) return r;
+        } else {
+            HIP_TRY(c, hipGetLastError());
+        }
+        if (prof) {
+            HIP_TRY(c, hipEventRecord(ev.b, st));
+            l.events.push_back(ev);
+        }
+    }
+    return 0;
+}
+
+}  // namespace vk
+
+extern "C" {
+
+// The pipelined form of vello_hip_render for animations: every frame brings its own scene.  The scene goes into
+// the private slot of the next lane of the rotation (only THAT lane's previous frame is waited for), the frame is
+// enqueued, and the call returns; other lanes keep rendering while the next scene crosses PCIe.
+int vello_hip_render_frame(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                           const vello_hip_render_params *params, const uint32_t *ramps, uint32_t n_ramps, void *out_device,
+                           size_t out_stride) {
+    if (!c || !params) return VELLO_HIP_E_INVALID;
+    if (int tr = check_target(c, params, out_device, out_stride, true)) return tr;
+    const auto set_up = [&](Lane &l, bool &) -> int {
+        HIP_TRY(c, hipStreamSynchronize(l.stream));
+        if (int r = load_slot(c, l.own, l.stream, scene, scene_len, layout, ramps, n_ramps)) return r;
+        l.use_own = true;
+        return 0;
+    };
+    return enter_frame(c, params, out_device, out_stride, true, VELLO_HIP_STAGE_FINE, set_up, no_step, no_step);
+}
+
+int vello_hip_render_resident(vello_hip_ctx *c, const vello_hip_render_params *params, void *out_device, size_t out_stride) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    if (int r = check_target(c, params, out_device, out_stride, true)) return r;
+    const auto set_up = [&](Lane &l, bool &new_scene) -> int {
+        new_scene = l.use_own;
+        if (!l.use_own) return 0;
+        // the lane last rendered a vello_hip_render_frame scene: resident frames always show the scene of
+        // vello_hip_upload_scene, whichever lane the rotation has reached
+        if (!c->shared.resident) {
+            c->last_error = "no scene uploaded (vello_hip_render_frame scenes are private to their frame)";
+            return VELLO_HIP_E_INVALID;
+        }
+        HIP_TRY(c, hipStreamSynchronize(l.stream));
+        l.use_own = false;
+        return 0;
+    };
+    int last = VELLO_HIP_STAGE_FINE;
+    if (const uint32_t ls = (c->debug_flags >> VELLO_HIP_DEBUG_LAST_STAGE_SHIFT) & 15u) last = (int)ls - 1 < last ? (int)ls - 1 : last;  // (measurement seam)
+    return enter_frame(c, params, out_device, out_stride, true, last, set_up, no_step, no_step);
+}
+
+int vello_hip_run_stages(vello_hip_ctx *c, const vello_hip_render_params *params, int first, int last) {
+    if (!c || first < 0 || last >= VELLO_HIP_STAGE_COUNT || first > last) return VELLO_HIP_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Lane &l = c->lanes[c->last_lane];
+    Frame f;
+    int r = prepare_frame(c, l, params, nullptr, 0, f, true);
+    if (r) return r;
+    if ((r = run_stage_range(c, l, f, first, last))) return r;
+    HIP_TRY(c, hipStreamSynchronize(l.stream));
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_get_bump(vello_hip_ctx *c, vello_hip_bump *out) {
+    if (!c || !out || !c->lanes[c->last_lane].zero_region.ptr) return VELLO_HIP_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Lane &l = c->lanes[c->last_lane];
+    HIP_TRY(c, hipStreamSynchronize(l.stream));
+    HIP_TRY(c, hipMemcpy(out, l.zero_region.ptr, sizeof(vello_hip_bump), hipMemcpyDeviceToHost));
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_sync_frame(vello_hip_ctx *c, uint32_t age) {
+    if (!c || age >= c->n_active) return VELLO_HIP_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t n = c->n_active;
+    Lane &l = c->lanes[(c->last_lane + n - age) % n];
+    HIP_TRY(c, hipStreamSynchronize(l.stream));
+    // (once per scene: what flatten counted, so that later frames can leave out a launch that would exit at once)
+    SceneSlot &sc = slot_of(c, l);
+    if (l.used && l.flatten_ran && l.zero_region.ptr && l.frame_generation == sc.generation && (sc.stroke_lines < 0 || (l.slices_on && sc.slice_demand < 0))) {
+        Control ctl;
+        HIP_TRY(c, hipMemcpy(&ctl, l.zero_region.ptr, sizeof ctl, hipMemcpyDeviceToHost));
+        if (ctl.bump.failed == 0u) learn_from_frame(sc, ctl, l);
+    }
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_sync(vello_hip_ctx *c) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int r = sync_all(c);
+    if (r) return r;
+    if (!c->have_cfg) return VELLO_HIP_OK;
+    // only the lanes of the current rotation: a lane dropped by set_frames_in_flight keeps its old control block
+    int first = VELLO_HIP_OK;
+    for (uint32_t i = 0; i < c->n_active && i < c->lanes.size(); i++) {
+        r = check_lane(c, c->lanes[i]);
+        if (r == VELLO_HIP_E_HIP) return r;
+        if (r && !first) first = r;
+    }
+    return first;
+}
+
+uint32_t vello_hip_last_render_attempts(vello_hip_ctx *c) { return c ? c->last_render_attempts : 0u; }
+uint64_t vello_hip_fused_launches(vello_hip_ctx *c) { return c ? c->fused_launches : 0u; }
+
+void *vello_hip_get_stream(vello_hip_ctx *c) { return c ? (void *)c->lanes[c->last_lane].stream : nullptr; }
+
+int vello_hip_set_auto_grow(vello_hip_ctx *c, int enabled) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    c->auto_grow = enabled != 0;
+    return VELLO_HIP_OK;
+}
+
+// A frame takes the setting when it is prepared (Frame::viewport_cull travels to flatten's kernels by value), so frames already
+// enqueued keep theirs.  The scene's remembered soup size (SceneSlot::soup_lines) only picks path_count's chunk size -- its grid
+// strides over the pool -- so a frame after a toggle is at worst cut into the other chunk size once.
+int vello_hip_set_viewport_cull(vello_hip_ctx *c, int enabled) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    c->viewport_cull = enabled != 0;
+    return VELLO_HIP_OK;
+}
+
+// As the culling switch: a frame takes the view when it is prepared (Frame::view travels to k_view_transforms by value, and the
+// frame's composed transform words are its lane's own), so frames already enqueued keep theirs.  What the engine remembers of a
+// scene's earlier frames (SceneSlot) only picks among kernels and launch shapes that are all correct for any view: DESIGN.md 13.
+int vello_hip_set_view_transform(vello_hip_ctx *c, const float view[6]) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    if (!view) {
+        c->has_view = false;
+        return VELLO_HIP_OK;
+    }
+    for (int k = 0; k < 6; k++)
+        if (!(view[k] - view[k] == 0.0f)) {  // NaN or infinity
+            c->last_error = "set_view_transform: the view has an entry that is not finite";
+            return VELLO_HIP_E_INVALID;
+        }
+    c->has_view = true;
+    c->view = Xform{view[0], view[1], view[2], view[3], view[4], view[5]};
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_render(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                     const vello_hip_render_params *params, const uint32_t *ramps, uint32_t n_ramps, void *out_rgba8, size_t out_stride,
+                     int out_is_device, vello_hip_bump *bump_out) {
+    if (!c || !params) return VELLO_HIP_E_INVALID;
+    int r = check_target(c, params, out_rgba8, out_stride, out_is_device != 0);
+    if (r) return r;
+    if (c->auto_grow && (r = presize_pools(c, scene, scene_len, layout, params))) return r;
+    r = vello_hip_upload_scene(c, scene, scene_len, layout, ramps, n_ramps);
+    if (r) return r;
+    int sync_r = VELLO_HIP_OK;
+    // robust mode: re-run with grown pools until the frame fits (each overflowing stage hides the demand of
+    // the stages behind it, so a handful of rounds at most)
+    for (int attempt = 0; attempt < 8; attempt++) {
+        c->last_render_attempts = (uint32_t)attempt + 1u;
+        r = vello_hip_render_resident(c, params, out_is_device ? out_rgba8 : nullptr, out_stride);
+        if (r) return r;
+        Lane &l = c->lanes[c->last_lane];
+        HIP_TRY(c, hipStreamSynchronize(l.stream));
+        vello_hip_bump b;
+        HIP_TRY(c, hipMemcpy(&b, l.zero_region.ptr, sizeof b, hipMemcpyDeviceToHost));
+        sync_r = check_lane(c, l);  // this frame's lane only: another lane's older failure is not this frame's
+        if (bump_out) *bump_out = b;
+        if (sync_r != VELLO_HIP_E_CAPACITY || !c->auto_grow) break;
+        if (vello_hip_grow_pools(c, &b, nullptr) != VELLO_HIP_OK) break;
+    }
+    if (sync_r) return sync_r;
+    if (out_rgba8 && !out_is_device) {
+        size_t row = (size_t)params->width * 4u;
+        HIP_TRY(c, hipMemcpy2D(out_rgba8, row_stride(params, out_stride), c->lanes[c->last_lane].buf[VELLO_HIP_BUF_OUTPUT].ptr, row, row, params->height,
+                               hipMemcpyDeviceToHost));
+    }
+    return VELLO_HIP_OK;
+}
+
+}  // extern "C"

@@ -247,7 +247,7 @@ struct PcWalk {
     float a, b, x0, y0;
     uint32_t ioff, count;        // crossing index of the line's item q (counted over the wave's 64 lines): ioff + q
     uint32_t base;               // tile index of (x, y) = base + y * stride + x
-    uint32_t bbox02;             // bbox0 | bbox2 << 16 (tile coordinates of a target of at most 65 535 tiles, engine.hip)
+    uint32_t bbox02;             // bbox0 | bbox2 << 16 (tile coordinates of a target of at most 65 535 tiles, configure in frames.hip)
     uint32_t flags;              // 1: is_down, 2: negative slope, 4: y0 == s0.y
 };
 

@@ -1,0 +1,197 @@
+// Device-side operations on scene data outside the pipeline's stages: atlas copies, the view's transform words, scene composition.
+#include "engine.h"
+
+namespace vk {
+
+// k_atlas_copy: the rectangles of one vello_hip_copy_images_device call as ONE concatenated texel space, cut into chunks of
+// `steps` x 256 texels, a chunk per workgroup.  Lane i of a wave takes texel base + i, so a wave reads and writes 64
+// consecutive dwords of a row (or the tail of one row and the head of the next); a thousand 16x16 sprites are 1 000
+// workgroups of full waves, not 16 000 rows of quarter waves, and a 4K frame is 2 000 workgroups.  A thread finds its
+// first texel's rectangle by binary search over the host's prefix and walks on from there by the 256-texel step.
+// Plain dword accesses: the atlas x is arbitrary, so a destination row is only 4-byte aligned.
+constexpr uint32_t ATLAS_COPY_MAX_STEPS = 16u, ATLAS_COPY_TARGET_WGS = 2048u;
+
+__global__ void __launch_bounds__(256) k_atlas_copy(const AtlasCopyDesc *__restrict__ descs, uint32_t n, uint64_t total, uint32_t steps,
+                                                    uint32_t *__restrict__ atlas, uint32_t atlas_w) {
+    uint64_t t = (uint64_t)blockIdx.x * steps * 256u + threadIdx.x;
+    if (t >= total) return;
+    uint32_t lo = 0u, hi = n - 1u;  // the last entry whose first <= t
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (descs[mid].first <= t) lo = mid;
+        else hi = mid - 1u;
+    }
+    uint32_t r = lo;
+    AtlasCopyDesc d = descs[r];
+    uint64_t local = t - d.first;
+    for (uint32_t k = 0; k < steps && t < total; k++, t += 256u, local += 256u) {
+        uint64_t size = (uint64_t)d.width * d.height;
+        while (local >= size) {  // (t < total: a later entry holds it; every entry of the table holds texels)
+            local -= size;
+            d = descs[++r];
+            size = (uint64_t)d.width * d.height;
+        }
+        const uint32_t li = (uint32_t)local;  // < width * height <= 65535^2
+        const uint32_t row = li / d.width, col = li - row * d.width;
+        const uint32_t v = *(const uint32_t *)(uintptr_t)(d.src + (uint64_t)row * d.src_stride + (uint64_t)col * 4u);
+        atlas[d.dst + (uint64_t)row * atlas_w + col] = v;
+    }
+}
+
+void launch_atlas_copy(const AtlasCopyDesc *descs, uint32_t n, uint64_t total, uint32_t *atlas, uint32_t atlas_w, hipStream_t s) {
+    // enough steps per workgroup that the grid stays near ATLAS_COPY_TARGET_WGS (8 per CU), at most ATLAS_COPY_MAX_STEPS
+    uint64_t steps = (total + 256u * ATLAS_COPY_TARGET_WGS - 1u) / (256u * ATLAS_COPY_TARGET_WGS);
+    steps = steps < 1u ? 1u : steps > ATLAS_COPY_MAX_STEPS ? ATLAS_COPY_MAX_STEPS : steps;
+    const uint64_t wgs = (total + steps * 256u - 1u) / (steps * 256u);
+    hipLaunchKernelGGL(k_atlas_copy, dim3((uint32_t)wgs), dim3(256), 0, s, descs, n, total, (uint32_t)steps, atlas, atlas_w);
+}
+
+// k_view_transforms: the view transform of vello_hip_set_view_transform composed into a frame's own copy of the transform stream, a
+// lane per entry.  Slot i of `out` is entry i - 1: slot 0 is the six words BELOW the stream, copied verbatim (a path encoded before any
+// transform reads them, read_transform in common.h; zeros when the scene has no six words there -- the pathtag scan then hands out no
+// index -1), slots 1 .. n_xf are V.T as vello_encoding's Transform::mul computes it (math.rs:51-73): f32, every product and every sum
+// rounded on its own (the tree is built without fp contraction), in this operand order and association.  Six dword loads and six
+// dword stores per lane at a stride of 24 bytes: the stream is 4-byte aligned only, and a wave's 64 entries are 1.5 KB of
+// consecutive memory either way.  The kernel reads the scene and writes the copy; nothing else of the frame runs beside it on
+// the lane's stream.
+__global__ void __launch_bounds__(256) k_view_transforms(const uint32_t *__restrict__ scene, uint32_t transform_base, uint32_t n_xf, Xform v,
+                                                         uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i > n_xf) return;
+    uint32_t *o = out + (size_t)i * 6u;
+    if (i == 0u) {
+        const bool below = transform_base >= 6u;
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) o[k] = below ? scene[transform_base - 6u + k] : 0u;
+        return;
+    }
+    const Xform t = read_transform(scene, transform_base, i - 1u);
+    const float m0 = v.m0 * t.m0 + v.m2 * t.m1, m1 = v.m1 * t.m0 + v.m3 * t.m1;
+    const float m2 = v.m0 * t.m2 + v.m2 * t.m3, m3 = v.m1 * t.m2 + v.m3 * t.m3;
+    const float t0 = (v.m0 * t.t0 + v.m2 * t.t1) + v.t0, t1 = (v.m1 * t.t0 + v.m3 * t.t1) + v.t1;
+    o[0] = __float_as_uint(m0);
+    o[1] = __float_as_uint(m1);
+    o[2] = __float_as_uint(m2);
+    o[3] = __float_as_uint(m3);
+    o[4] = __float_as_uint(t0);
+    o[5] = __float_as_uint(t1);
+}
+
+void launch_view_transforms(const Frame &f, hipStream_t s) {
+    const uint32_t n_xf = (f.cfg.layout.style_base - f.cfg.layout.transform_base) / 6u;
+    // (slot 0 of the copy is entry -1: six words in front of xf_base)
+    hipLaunchKernelGGL(k_view_transforms, dim3((n_xf + 1u + 255u) / 256u), dim3(256), 0, s, f.scene, f.cfg.layout.transform_base, n_xf, f.view,
+                       const_cast<uint32_t *>(f.scene) + (f.xf_base - 6u));
+}
+
+// k_compose_scene: a frame's packed scene written from instances of the library's fragments (vello_hip_render_instances; the contract is
+// in include/vello_hip.h, the arguments in engine.h).  A thread per destination word, a workgroup per chunk of steps x 256 consecutive
+// words of ONE stream, lane i of a wave on word base + i as in k_atlas_copy.  Which instance a word belongs to is a search for the last
+// entry of the stream's prefix that is <= the word's offset (empty instances repeat an offset; the last one of a run is the one that
+// holds words).  Fragments may be a dozen words long, so the search is the cost: threads 0 and 64 find the chunk's first and last
+// instance in the table, the workgroup copies that slice of the prefix into LDS, and every thread searches the slice, from the
+// instance of its previous word on.  The staging area holds an entry per word of the largest chunk plus two, which is every slice of
+// a word stream without empty instances (an instance that holds words holds at least one).  A slice can be longer where empty
+// instances lie in between and, in the tag stream, where fragments are shorter than four tags (a word holds up to four one-tag
+// instances): such a chunk is not staged and its threads search the table itself.
+//   word streams   a dword copy from the library;
+//   transforms     word k of an entry needs two words of T and two or three of V: V.T as k_view_transforms computes it;
+//   tags           byte-granular: where the four tags of a word come from one instance, two dword loads and a funnel shift; a word
+//                  that straddles instances (or the stream's end) is put together from byte loads.  Words of the padding are zero.
+constexpr uint32_t COMPOSE_LDS_OFFSETS = COMPOSE_MAX_STEPS * 256u + 2u;
+
+__global__ void __launch_bounds__(256) k_compose_scene(ComposeArgs a) {
+    __shared__ uint32_t s_off[COMPOSE_LDS_OFFSETS];
+    __shared__ uint32_t s_ends[2];
+    const uint32_t bid = blockIdx.x, tid = threadIdx.x;
+    uint32_t s = 0u;
+#pragma unroll
+    for (uint32_t k = 1u; k < 7u; k++) s += a.wg_first[k] <= bid ? 1u : 0u;  // (non-decreasing: the last stream that starts at or before bid)
+    if (s == 6u) {
+        if (tid < 16u) a.dst[(size_t)a.dst_base[5] + a.len[5] + tid] = 0u;
+        return;
+    }
+    const uint32_t chunk = a.steps * 256u;
+    const uint32_t lo = (bid - a.wg_first[s]) * chunk;                         // < len[s]: the host launches ceil(len / chunk) workgroups
+    const uint32_t rem = a.len[s] - lo < chunk ? a.len[s] - lo : chunk;        // words of this chunk
+    // the chunk in the units of the stream's prefix (bytes for tags: the host keeps the padded tag bytes within u32)
+    const uint32_t ulo = s == 0u ? lo * 4u : lo;
+    uint32_t uend = s == 0u ? (lo + rem) * 4u : lo + rem;
+    if (s == 0u && uend > a.tag_bytes) uend = a.tag_bytes;
+    const bool any = ulo < uend;  // (else: a chunk of the tags' padding)
+    const uint32_t *off = a.table + (size_t)s * (a.n + 1u);
+    const uint32_t *frag_of = a.table + 6u * ((size_t)a.n + 1u);
+    if (any && (tid == 0u || tid == 64u)) {
+        const uint32_t x = tid == 0u ? ulo : uend - 1u;
+        uint32_t i = 0u, h = a.n - 1u;  // (any: some instance holds x, so n > 0)
+        while (i < h) {
+            const uint32_t mid = (i + h + 1u) >> 1;
+            if (off[mid] <= x) i = mid;
+            else h = mid - 1u;
+        }
+        s_ends[tid >> 6] = i;
+    }
+    __syncthreads();
+    const uint32_t first = any ? s_ends[0] : 0u, last = any ? s_ends[1] : 0u;
+    const uint32_t m = last - first + 2u;  // off[first .. last + 1]
+    const bool staged = any && m <= COMPOSE_LDS_OFFSETS;
+    if (staged)
+        for (uint32_t k = tid; k < m; k += 256u) s_off[k] = off[first + k];
+    __syncthreads();
+    auto at = [&](uint32_t i) -> uint32_t { return staged ? s_off[i - first] : off[i]; };  // first <= i <= last + 1
+    uint32_t cur = first;
+    for (uint32_t k = 0u; k < a.steps; k++) {
+        const uint32_t idx = k * 256u + tid;
+        if (idx >= rem) break;
+        const uint32_t l = lo + idx;
+        uint32_t *d = a.dst + (size_t)a.dst_base[s] + l;
+        const uint32_t x = s == 0u ? l * 4u : l;
+        if (x >= uend) {  // the tags' padding
+            *d = 0u;
+            continue;
+        }
+        uint32_t i = cur, h = last;
+        while (i < h) {
+            const uint32_t mid = (i + h + 1u) >> 1;
+            if (at(mid) <= x) i = mid;
+            else h = mid - 1u;
+        }
+        cur = i;
+        const uint32_t o = at(i);
+        const uint32_t begin = a.frags[(size_t)frag_of[i] * 6u + s];
+        if (s == 0u) {
+            if (x + 4u <= at(i + 1u)) {
+                const uint32_t sb = begin + (x - o);  // byte of the library's tag stream
+                const uint32_t *p = a.lib + (size_t)a.src_base[0] + (sb >> 2);
+                const uint32_t sh = (sb & 3u) * 8u;
+                const uint32_t w0 = p[0], w1 = sh ? p[1] : 0u;
+                *d = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
+            } else {
+                const uint8_t *tags = reinterpret_cast<const uint8_t *>(a.lib + (size_t)a.src_base[0]);
+                uint32_t v = 0u, j = i;
+                for (uint32_t b = 0u; b < 4u; b++) {
+                    const uint32_t pos = x + b;
+                    if (pos >= uend) break;  // (the stream's end: uend == tag_bytes here)
+                    while (pos >= at(j + 1u)) j++;  // (pos < uend: an instance <= last holds it)
+                    v |= (uint32_t)tags[(size_t)a.frags[(size_t)frag_of[j] * 6u] + (pos - at(j))] << (8u * b);
+                }
+                *d = v;
+            }
+        } else if (s == 4u) {
+            const uint32_t r = x - o, comp = r % 6u, pair = comp >> 1, odd = comp & 1u;
+            const uint32_t *t = a.lib + (size_t)a.src_base[4] + begin + (r - comp) + 2u * pair;
+            const uint32_t *v = frag_of + a.n + (size_t)i * 6u;
+            float c = __uint_as_float(v[odd]) * __uint_as_float(t[0]) + __uint_as_float(v[2u + odd]) * __uint_as_float(t[1]);
+            if (pair == 2u) c = c + __uint_as_float(v[4u + odd]);
+            *d = __float_as_uint(c);
+        } else {
+            *d = a.lib[(size_t)a.src_base[s] + begin + (x - o)];
+        }
+    }
+}
+
+void launch_compose_scene(const ComposeArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(k_compose_scene, dim3(a.wg_first[6] + 1u), dim3(256), 0, s, a);
+}
+
+}  // namespace vk

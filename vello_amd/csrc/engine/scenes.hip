@@ -1,0 +1,402 @@
+// Scenes: making a packed scene resident in a slot, the shared scene as a library of fragments, frames composed from instances.
+#include <cstring>
+
+#include "ctx.h"
+
+using namespace vk;
+
+namespace {
+
+// ensure() for a slot's scene buffer: `bytes` of scene (what VELLO_HIP_BUF_SCENE shows) and, from the next 16-byte boundary on, a
+// tail of `tail` bytes for the composed transform words.  Like ensure() it never shrinks -- neither part: the tail's capacity is
+// kept in a field of its own, written only where the allocation happens, so that scenes whose transform counts go up and down
+// (a lane's vello_hip_render_frame scenes) settle on the largest and allocate nothing from then on.
+int ensure_scene(vello_hip_ctx *c, SceneSlot &sc, size_t bytes, size_t tail) {
+    if (sc.scene.ptr && sc.scene.size >= bytes && sc.view_cap_bytes >= tail) return 0;
+    const size_t visible = sc.scene.size > bytes ? sc.scene.size : bytes;
+    const size_t cap = sc.view_cap_bytes > tail ? sc.view_cap_bytes : tail;
+    if (sc.scene.ptr) HIP_TRY(c, hipFree(sc.scene.ptr));
+    sc.scene.ptr = nullptr;
+    sc.scene.size = 0;
+    sc.view_cap_bytes = 0;
+    const size_t at = (visible + 15u) & ~(size_t)15u;
+    HIP_TRY(c, hipMalloc(&sc.scene.ptr, at + cap + 256));
+    sc.scene.size = visible;
+    sc.view_at = at / 4u;
+    sc.view_cap_bytes = cap;
+    c->scene_allocations++;
+    return 0;
+}
+
+// Whether `layout` describes a buffer of scene_len bytes (the streams' contents are judged by load_slot and the pathtag scan)
+int check_layout(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout) {
+    if ((!scene && scene_len) || !layout || (scene_len & 3u)) return VELLO_HIP_E_INVALID;
+    const vello_hip_layout &L = *layout;
+    size_t words = scene_len / 4u;
+    if (L.path_tag_base > L.path_data_base || L.path_data_base > L.draw_tag_base || L.draw_tag_base > L.draw_data_base ||
+        L.draw_data_base > L.transform_base || L.transform_base > L.style_base || L.style_base > words ||
+        (size_t)L.draw_tag_base + L.n_draw_objects > words) {
+        c->last_error = "layout does not describe the scene buffer";
+        return VELLO_HIP_E_INVALID;
+    }
+    if ((((size_t)L.path_data_base - L.path_tag_base) * 4u) % 1024u != 0u) {
+        c->last_error = "path tag stream is not padded to 4*256 tags (resolve.rs:622-639)";
+        return VELLO_HIP_E_INVALID;
+    }
+    return VELLO_HIP_OK;
+}
+
+// Sizes the slot for a scene of this (checked) layout and length and forgets what earlier frames told of the scene it held: what
+// load_slot does before it copies the bytes, and vello_hip_render_instances before k_compose_scene writes them.
+int size_slot(vello_hip_ctx *c, SceneSlot &sc, const vello_hip_layout &L, size_t scene_len) {
+    int r;
+    // 64 B of slack: flatten reads tag ix+1 and the (wrapped) style word of pre-style tags speculatively
+    // ... and, behind them, room for the composed transform words of frames with a view (SceneSlot::view_at)
+    const uint32_t set_words = ((L.style_base - L.transform_base) / 6u + 1u) * 6u;
+    const uint32_t sets = &sc == &c->shared ? MAX_LANES : 1u;
+    if ((r = ensure_scene(c, sc, scene_len + 64, (size_t)set_words * sets * 4u))) return r;
+    sc.view_sets = sets;
+    sc.view_set_words = set_words;
+    sc.layout = L;
+    sc.scene_len = scene_len;
+    uint32_t n_path_tags = (L.path_data_base - L.path_tag_base) * 4u;
+    sc.n_tag_words = align_up(n_path_tags, 1024u) / 4u;
+    sc.n_pathtag_parts = (sc.n_tag_words + PATHTAG_PART_WORDS - 1u) / PATHTAG_PART_WORDS;
+    if (sc.n_pathtag_parts == 0) sc.n_pathtag_parts = 1;
+    sc.n_draw_parts = (L.n_draw_objects + DRAW_PART - 1u) / DRAW_PART;
+    sc.zero_bytes = sizeof(Control) + ((size_t)sc.n_pathtag_parts * 10u + (size_t)sc.n_draw_parts * 8u) * 8u;
+    // Which fine specialisation the scene needs: any draw tag other than COLOR / BEGIN_CLIP / END_CLIP / NOP
+    // (draw.rs:15-51) makes coarse emit a gradient, image or blur command.
+    sc.brushes = false;
+    sc.composed = false;
+    sc.stroke_lines = -1;
+    sc.heavy_curves = sc.heavy_strokes = -1;
+    sc.soup_lines = -1;
+    sc.slice_demand = -1;
+    sc.generation += 1u;
+    return VELLO_HIP_OK;
+}
+
+// One fragment against the host bytes of its (checked) library: the rules of vello_hip_upload_fragments in include/vello_hip.h.
+int check_fragment(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout &L, const vello_hip_fragment &fr,
+                          uint32_t index, FragmentInfo &out) {
+    auto refuse = [&](const char *why) {
+        c->last_error = "upload_fragments: fragment " + std::to_string(index) + ": " + why;
+        return VELLO_HIP_E_INVALID;
+    };
+    const uint32_t *words = reinterpret_cast<const uint32_t *>(scene);
+    const uint64_t n_words = scene_len / 4u;
+    const uint32_t draws_room = L.draw_data_base - L.draw_tag_base;
+    // the streams' lengths and what one entry is in the units of ComposeArgs
+    const uint64_t stream_len[6] = {((uint64_t)L.path_data_base - L.path_tag_base) * 4u, (uint64_t)L.draw_tag_base - L.path_data_base,
+                                    L.n_draw_objects < draws_room ? L.n_draw_objects : draws_room, (uint64_t)L.transform_base - L.draw_data_base,
+                                    ((uint64_t)L.style_base - L.transform_base) / 6u, (n_words - L.style_base) / STYLE_SIZE_IN_WORDS};
+    const uint32_t unit[6] = {1u, 1u, 1u, 1u, 6u, STYLE_SIZE_IN_WORDS};
+    const uint32_t *range[6] = {fr.path_tags, fr.path_data, fr.draws, fr.draw_data, fr.transforms, fr.styles};
+    uint32_t n_entries[6];
+    for (int s = 0; s < 6; s++) {
+        if (range[s][0] > range[s][1] || range[s][1] > stream_len[s]) return refuse("a range is not ordered or leaves its stream");
+        n_entries[s] = range[s][1] - range[s][0];
+        out.begin[s] = range[s][0] * unit[s];  // (<= the stream's words: no overflow)
+        out.len[s] = n_entries[s] * unit[s];
+    }
+    const uint8_t *tags = scene + (size_t)L.path_tag_base * 4u;
+    uint32_t n_path = 0, n_xf = 0, n_style = 0;
+    bool has_xf = false, has_style = false;
+    for (uint32_t i = fr.path_tags[0]; i < fr.path_tags[1]; i++) {
+        const uint32_t t = tags[i];
+        if (((t & PATH_TAG_SEG_TYPE) != 0u || (t & PATH_TAG_PATH) != 0u) && !(has_xf && has_style))
+            return refuse("a segment or PATH tag comes before the fragment's first TRANSFORM and STYLE markers");
+        if (t & PATH_TAG_PATH) n_path++;
+        if (t & PATH_TAG_TRANSFORM) n_xf++, has_xf = true;
+        if (t & PATH_TAG_STYLE) n_style++, has_style = true;
+    }
+    if (n_path != n_entries[2]) return refuse("`draws` is not as long as the tag range has PATH markers");
+    if (n_xf != n_entries[4] || n_style != n_entries[5]) return refuse("`transforms` / `styles` are not as long as the tag range has TRANSFORM / STYLE markers");
+    uint64_t draw_data_words = 0, info_words = 0;
+    uint32_t clip_tags = 0, depth = 0;
+    out.brushes = false;
+    for (uint32_t i = fr.draws[0]; i < fr.draws[1]; i++) {
+        const uint32_t t = words[L.draw_tag_base + i];
+        if (t != DRAWTAG_FILL_COLOR && t != DRAWTAG_BEGIN_CLIP && t != DRAWTAG_END_CLIP && t != DRAWTAG_NOP) out.brushes = true;
+        clip_tags += t & 1u;
+        draw_data_words += (t >> 2) & 0x7u;
+        info_words += (t >> 6) & 0xfu;
+        if (t == DRAWTAG_BEGIN_CLIP) depth++;
+        if (t == DRAWTAG_END_CLIP) {
+            if (depth == 0u) return refuse("an END_CLIP without a BEGIN_CLIP before it in the fragment");
+            depth--;
+        }
+    }
+    if (depth != 0u) return refuse("a BEGIN_CLIP is left open");
+    if (draw_data_words != n_entries[3]) return refuse("`draw_data` is not as long as the fragment's draw tags ask for");
+    if (info_words > 0xffffffffull) return refuse("more than 2^32 info words");  // (up to 15 per draw tag)
+    out.n_clips = clip_tags;
+    out.info_words = (uint32_t)info_words;
+    return VELLO_HIP_OK;
+}
+
+// The composed scene of an instance list: its layout, its length, what fine needs to know of it, and the sums the table is built from.
+struct ComposePlan {
+    vello_hip_layout layout;
+    size_t scene_len;
+    uint32_t len[6];      // per stream, in the units of ComposeArgs (tags: bytes, without the padding)
+    uint32_t tag_words;   // the tag stream with its padding
+    bool brushes;
+};
+
+int plan_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, ComposePlan &p) {
+    if (!c->have_fragments || !c->shared.resident) {
+        c->last_error = "no fragment table (vello_hip_upload_fragments)";
+        return VELLO_HIP_E_INVALID;
+    }
+    if (n > 0u && !inst) {
+        c->last_error = "instances: inst is NULL";
+        return VELLO_HIP_E_INVALID;
+    }
+    uint64_t len[6] = {}, n_clips = 0, info = 0;
+    p.brushes = false;
+    const size_t n_frags = c->fragments.size();
+    for (uint32_t i = 0; i < n; i++) {
+        if (inst[i].fragment >= n_frags) {
+            c->last_error = "instance " + std::to_string(i) + ": fragment " + std::to_string(inst[i].fragment) + " of " + std::to_string(n_frags);
+            return VELLO_HIP_E_INVALID;
+        }
+        for (int k = 0; k < 6; k++)
+            if (!(inst[i].transform[k] - inst[i].transform[k] == 0.0f)) {  // NaN or infinity
+                c->last_error = "instance " + std::to_string(i) + ": the transform has an entry that is not finite";
+                return VELLO_HIP_E_INVALID;
+            }
+        const FragmentInfo &fi = c->fragments[inst[i].fragment];
+        for (int s = 0; s < 6; s++) len[s] += fi.len[s];
+        n_clips += fi.n_clips;
+        info += fi.info_words;
+        p.brushes = p.brushes || fi.brushes;
+    }
+    // (sums of at most 2^32 terms below 2^32: no u64 overflow)
+    const uint64_t tag_bytes_padded = (len[0] + 1023u) & ~(uint64_t)1023u;
+    const uint64_t total = tag_bytes_padded / 4u + len[1] + len[2] + len[3] + len[4] + len[5];
+    if (total >= ((uint64_t)1 << 32) || tag_bytes_padded >= ((uint64_t)1 << 32) || n_clips > 0xffffffffull || info > 0xffffffffull) {
+        c->last_error = "instances: the composed scene has 2^32 words or more, or a count that leaves u32";
+        return VELLO_HIP_E_INVALID;
+    }
+    for (int s = 0; s < 6; s++) p.len[s] = (uint32_t)len[s];
+    p.tag_words = (uint32_t)(tag_bytes_padded / 4u);
+    vello_hip_layout &L = p.layout;
+    L.n_draw_objects = L.n_paths = p.len[2];
+    L.n_clips = (uint32_t)n_clips;
+    L.bin_data_start = (uint32_t)info;
+    L.path_tag_base = 0u;
+    L.path_data_base = p.tag_words;
+    L.draw_tag_base = L.path_data_base + p.len[1];
+    L.draw_data_base = L.draw_tag_base + p.len[2];
+    L.transform_base = L.draw_data_base + p.len[3];
+    L.style_base = L.transform_base + p.len[4];
+    p.scene_len = (size_t)total * 4u;
+    return VELLO_HIP_OK;
+}
+
+}  // namespace
+
+namespace vk {
+
+// Validates the layout, sizes the slot and copies scene + ramps on `st`; returns once the source buffers may be
+// reused (they are caller-owned only for the duration of the call, recording.rs:124-129).
+int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *scene, size_t scene_len,
+                     const vello_hip_layout *layout, const uint32_t *ramps, uint32_t n_ramps) {
+    int r;
+    if ((r = check_layout(c, scene, scene_len, layout))) return r;
+    const vello_hip_layout &L = *layout;
+    if ((r = size_slot(c, sc, L, scene_len))) return r;
+    {
+        // The same pass checks what draw_leaf / clip_leaf will index with (shared/drawtag.wgsl:47-54: bit 0 = clip,
+        // bits 2-4 = draw data words, bits 6-9 = info words).  WebGPU's robust buffer access absorbs an inconsistent
+        // stream upstream; here it must be refused.  (The path tag stream is checked by the pathtag scan, on the GPU.)
+        const uint32_t *words_p = reinterpret_cast<const uint32_t *>(scene);
+        uint64_t draw_data_words = 0, info_words = 0, clip_tags = 0;
+        for (uint32_t i = 0; i < L.n_draw_objects; i++) {
+            uint32_t t = words_p[L.draw_tag_base + i];
+            if (t != DRAWTAG_FILL_COLOR && t != DRAWTAG_BEGIN_CLIP && t != DRAWTAG_END_CLIP && t != DRAWTAG_NOP) sc.brushes = true;
+            clip_tags += t & 1u;
+            draw_data_words += (t >> 2) & 0x7u;
+            info_words += (t >> 6) & 0xfu;
+        }
+        // clip_tags == n_clips, not <=: k_clip walks n_clips entries of clip_inp and draw_leaf writes one per clip tag
+        // (resolve counts exactly the BEGIN/END_CLIP tags below n_draw_objects: the END_CLIPs it appends for unclosed
+        // layers lie behind them, resolve.rs:139-141); fewer tags would leave entries uninitialised
+        if (draw_data_words > (uint64_t)(L.transform_base - L.draw_data_base) || info_words > L.bin_data_start || clip_tags != L.n_clips ||
+            L.n_draw_objects > L.n_paths) {
+            c->last_error = "draw tags need more draw data / info words / paths than the layout provides, or their clip count differs from n_clips";
+            return VELLO_HIP_E_INVALID;
+        }
+    }
+    if (scene_len) HIP_TRY(c, hipMemcpyAsync(sc.scene.ptr, scene, scene_len, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync((char *)sc.scene.ptr + scene_len, 0, 64, st));
+    sc.n_ramps = 0;
+    if (ramps && n_ramps) {
+        if ((r = ensure(c, sc.ramps, (size_t)n_ramps * 512u * 4u))) return r;
+        HIP_TRY(c, hipMemcpyAsync(sc.ramps.ptr, ramps, (size_t)n_ramps * 512u * 4u, hipMemcpyHostToDevice, st));
+        sc.n_ramps = n_ramps;
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    sc.resident = true;
+    return VELLO_HIP_OK;
+}
+
+}  // namespace vk
+
+extern "C" {
+
+int vello_hip_upload_scene(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                           const uint32_t *ramps, uint32_t n_ramps) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int r;
+    // frames still in flight read the old scene
+    if ((r = sync_all(c))) return r;
+    c->have_fragments = false;  // (vello_hip_upload_fragments sets its table once the scene is resident)
+    c->fragments.clear();
+    if ((r = load_slot(c, c->shared, c->lanes[0].stream, scene, scene_len, layout, ramps, n_ramps))) return r;
+    for (auto &l : c->lanes) {
+        l.use_own = false;
+        if ((r = alloc_lane_scene(c, l, c->shared))) return r;
+    }
+    return VELLO_HIP_OK;
+}
+
+uint64_t vello_hip_scene_allocations(vello_hip_ctx *c) { return c ? c->scene_allocations : 0u; }
+
+int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout, const uint32_t *ramps,
+                               uint32_t n_ramps, const vello_hip_fragment *frags, uint32_t n_frags) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // whatever goes wrong from here on, nothing stays resident (frames in flight keep what they were enqueued with)
+    c->shared.resident = false;
+    c->have_fragments = false;
+    c->fragments.clear();
+    if (n_frags > 0u && !frags) {
+        c->last_error = "upload_fragments: frags is NULL";
+        return VELLO_HIP_E_INVALID;
+    }
+    int r;
+    if ((r = check_layout(c, scene, scene_len, layout))) return r;
+    std::vector<FragmentInfo> infos(n_frags);
+    for (uint32_t i = 0; i < n_frags; i++)
+        if ((r = check_fragment(c, scene, scene_len, *layout, frags[i], i, infos[i]))) return r;
+    if ((r = vello_hip_upload_scene(c, scene, scene_len, layout, ramps, n_ramps))) return r;
+    // (the lanes are idle: upload_scene waited for them, so no frame reads the table that ensure() may free)
+    std::vector<uint32_t> begins((size_t)n_frags * 6u);
+    for (uint32_t i = 0; i < n_frags; i++) std::memcpy(&begins[(size_t)i * 6u], infos[i].begin, sizeof infos[i].begin);
+    if ((r = ensure(c, c->frag_table, begins.size() * 4u))) {
+        c->shared.resident = false;
+        return r;
+    }
+    if (n_frags) {
+        const hipError_t e = hipMemcpy(c->frag_table.ptr, begins.data(), begins.size() * 4u, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            c->shared.resident = false;
+            c->last_error = std::string("upload_fragments: ") + hipGetErrorString(e);
+            return VELLO_HIP_E_HIP;
+        }
+    }
+    c->fragments = std::move(infos);
+    c->have_fragments = true;
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_instances_layout(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, vello_hip_layout *layout_out, size_t *scene_len_out) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    ComposePlan p;
+    if (int r = plan_instances(c, inst, n, p)) return r;
+    if (layout_out) *layout_out = p.layout;
+    if (scene_len_out) *scene_len_out = p.scene_len;
+    return VELLO_HIP_OK;
+}
+
+// vello_hip_render_frame with k_compose_scene in the host copy's place.  Everything that can refuse the frame is asked before the
+// lane is taken; the instance table goes through a pinned block to the lane's own table, on the lane's stream, ahead of the kernel.
+int vello_hip_render_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, const vello_hip_render_params *params, void *out_device,
+                               size_t out_stride) {
+    if (!c || !params) return VELLO_HIP_E_INVALID;
+    ComposePlan p;
+    int r = plan_instances(c, inst, n, p);
+    if (r) return r;
+    if ((r = check_target(c, params, out_device, out_stride, true))) return r;
+    const size_t table_bytes = compose_table_words(n) * 4u;
+    Staging *st = nullptr;
+    const auto set_up = [&](Lane &l, bool &) -> int {
+        HIP_TRY(c, hipStreamSynchronize(l.stream));
+        // The slot holds no scene until the frame is enqueued: a failure on the way leaves the lane without one, not with a
+        // composed scene whose bytes were never written.
+        l.own.resident = false;
+        if (int sr = size_slot(c, l.own, p.layout, p.scene_len)) return sr;
+        l.own.brushes = p.brushes;
+        l.own.composed = true;
+        l.own.n_ramps = 0;
+        l.use_own = true;
+        return 0;
+    };
+    const auto staged = [&](Lane &l) -> int {
+        if (int sr = acquire_staging(c, table_bytes, st)) return sr;
+        if (int sr = ensure(c, l.compose_table, table_bytes)) return sr;
+        l.own.resident = true;  // (prepare_frame asks for it)
+        return 0;
+    };
+    // the instance table and k_compose_scene, ahead of the stages
+    const auto enqueue = [&](Lane &l) -> int {
+        // the Config was not sent (a blocking copy): VELLO_HIP_BUF_CONFIG gets it when it is next read or written
+        c->cfg_unsent = true;
+        // the table (engine.h ComposeArgs): six exclusive prefixes, the fragment indices, the transforms
+        uint32_t *table = (uint32_t *)st->host;
+        {
+            uint32_t *off[6], run[6] = {};
+            for (int s = 0; s < 6; s++) off[s] = table + (size_t)s * (n + 1u);
+            uint32_t *frag_of = table + 6u * ((size_t)n + 1u);
+            for (uint32_t i = 0; i < n; i++) {
+                const FragmentInfo &fi = c->fragments[inst[i].fragment];
+                for (int s = 0; s < 6; s++) {
+                    off[s][i] = run[s];
+                    run[s] += fi.len[s];
+                }
+                frag_of[i] = inst[i].fragment;
+                std::memcpy(frag_of + n + (size_t)i * 6u, inst[i].transform, 24);
+            }
+            for (int s = 0; s < 6; s++) off[s][n] = run[s];
+        }
+        ComposeArgs a{};
+        a.lib = (const uint32_t *)c->shared.scene.ptr;
+        a.dst = (uint32_t *)l.own.scene.ptr;
+        a.table = (const uint32_t *)l.compose_table.ptr;
+        a.frags = (const uint32_t *)c->frag_table.ptr;
+        a.n = n;
+        const vello_hip_layout &S = c->shared.layout, &D = p.layout;
+        const uint32_t src_base[6] = {S.path_tag_base, S.path_data_base, S.draw_tag_base, S.draw_data_base, S.transform_base, S.style_base};
+        const uint32_t dst_base[6] = {D.path_tag_base, D.path_data_base, D.draw_tag_base, D.draw_data_base, D.transform_base, D.style_base};
+        const uint64_t total = p.scene_len / 4u;
+        uint64_t steps = (total + 256u * COMPOSE_TARGET_WGS - 1u) / (256u * COMPOSE_TARGET_WGS);
+        steps = steps < 1u ? 1u : steps > COMPOSE_MAX_STEPS ? COMPOSE_MAX_STEPS : steps;
+        a.steps = (uint32_t)steps;
+        uint32_t wg = 0u;
+        for (int s = 0; s < 6; s++) {
+            a.src_base[s] = src_base[s];
+            a.dst_base[s] = dst_base[s];
+            a.len[s] = s == 0 ? p.tag_words : p.len[s];
+            a.wg_first[s] = wg;
+            wg += (uint32_t)(((uint64_t)a.len[s] + steps * 256u - 1u) / (steps * 256u));  // (< 2^32 words / 256 in all)
+        }
+        a.wg_first[6] = wg;
+        a.tag_bytes = p.len[0];
+        l.own.resident = false;
+        HIP_TRY(c, hipMemcpyAsync(l.compose_table.ptr, st->host, table_bytes, hipMemcpyHostToDevice, l.stream));
+        HIP_TRY(c, hipEventRecord(st->done, l.stream));
+        st->busy = true;
+        launch_compose_scene(a, l.stream);
+        HIP_TRY(c, hipGetLastError());
+        l.own.resident = true;
+        return 0;
+    };
+    // (the rotation moves only once nothing can refuse the frame)
+    return enter_frame(c, params, out_device, out_stride, false, VELLO_HIP_STAGE_FINE, set_up, staged, enqueue);
+}
+
+}  // extern "C"
