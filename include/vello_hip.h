@@ -25,6 +25,8 @@
  *                              for Renderer::override_image / register_texture
  *   vello_hip_upload_fragments /  Scene::append(&other, Some(transform))  vello/src/scene.rs (append),
  *   vello_hip_render_instances    per instance + resolve + upload        vello_encoding/src/encoding.rs:95-152
+ *   vello_hip_render_instances_painted  ... each appended scene encoded  vello_encoding/src/encoding.rs:280-290
+ *                              with a solid brush of its own (encode_brush)
  *   vello_hip_sync             queue.submit + device.poll                vello/src/wgpu_engine.rs:757
  *   vello_hip_set_frames_in_flight  back-to-back queue.submit without waiting  vello/src/wgpu_engine.rs:757
  *   vello_hip_get_bump         the robust path's bump download           vello/src/lib.rs:730, :753-761
@@ -373,6 +375,42 @@ int vello_hip_instances_layout(vello_hip_ctx *ctx, const vello_hip_instance *ins
  * only the PTCL / info-word minimum of the target is sized), ramps or atlases per fragment, and unbalanced fragments. */
 int vello_hip_render_instances(vello_hip_ctx *ctx, const vello_hip_instance *inst, uint32_t n, const vello_hip_render_params *params,
                                void *out_device, size_t out_stride);
+
+/* Per-instance paint, parallel to the instance list: instance i of a fragment drawn in a solid colour of its own -- a glyph run's
+ * brush (Encoding::encode_brush, vello_encoding/src/encoding.rs:280-290), a tinted or highlighted symbol, a selection colour, a
+ * fade -- without a copy of the outline per colour in the library. */
+enum { VELLO_HIP_PAINT_KEEP = 0, VELLO_HIP_PAINT_SOLID = 1 };
+typedef struct vello_hip_paint {
+    uint32_t flags, rgba;   /* rgba: premultiplied RGBA8, R in the low byte -- a DrawColor word, as base_color */
+} vello_hip_paint;
+/* vello_hip_render_instances with `paints[i]` applied to instance i.
+ * The colour words of a fragment: walk its draw tags draws[0] .. draws[1] in order with a running offset d = 0 into its draw_data
+ * range; a tag t advances d by (t >> 2) & 7; word d of a tag equal to DRAWTAG_FILL_COLOR (0x44) or DRAWTAG_BLURRED_ROUNDED_RECT
+ * (0x2d4) is a colour word -- both hold a DrawColor first (vello_encoding/src/draw.rs:70-74, :175-186).  Nothing else is: not a
+ * gradient's index and points, not an image's words, not the four floats of a blurred rect, not BEGIN_CLIP's blend and alpha words.
+ * The rule is per fragment and relative to its own draw_data begin (fragments may overlap in the library).
+ * The composed scene is the one vello_hip_render_instances documents, with one more rule:
+ *   1b. Every colour word of instance i with paints[i].flags == VELLO_HIP_PAINT_SOLID becomes paints[i].rgba.  No other word
+ *       changes; the layout and length are those of vello_hip_instances_layout, whatever the paints.
+ *   - paints == NULL is vello_hip_render_instances (which is this call with NULL): the same frame, bit for bit in every buffer and
+ *     counter, from the same kernel and the same table of 52 bytes per instance.  A paint list adds 8 bytes per instance to it.
+ *   - A paint on an instance whose fragment has no colour word (gradient, image, clip-only, empty) and VELLO_HIP_PAINT_KEEP with
+ *     any rgba are legal and change nothing.  Any rgba is accepted, as any base_color is.
+ *   - VELLO_HIP_E_INVALID, with vello_hip_last_error naming the instance, for a flags value other than 0 or 1 -- like every refusal
+ *     of vello_hip_render_instances, all of which apply: nothing is enqueued, the rotation and VELLO_HIP_BUF_SCENE stay as they
+ *     were.  Also for a paint list on a library whose fragments' draw_data ranges add up to 2^32 words or more (no masks are kept
+ *     for it; unpainted frames of such a library are served as before).
+ *   - Paints belong to their frame: frames in flight may show one instance list under different paints, an unpainted frame that
+ *     follows a painted one on the same buffer set shows the library's colours, the library's bytes are never modified.  `paints`
+ *     may be reused when the call returns.
+ *   - Afterwards VELLO_HIP_BUF_SCENE / VELLO_HIP_BUF_CONFIG show the painted composed bytes and layout and vello_hip_run_stages
+ *     acts on them.  Composes with the view transform and viewport culling like any instance frame.  Coarse reads the composed
+ *     colours: an instance painted opaque may occlude what lies under it, the same instance painted translucent may not.
+ * Out of scope: alpha modulation of the library's colour (the host multiplies before it quantises, encoding.rs:280-290, so a
+ * stored premultiplied word cannot reproduce it: the caller passes the finished word); gradient, image and layer-alpha overrides;
+ * pool estimation for instance lists, which stays where vello_hip_render_instances left it. */
+int vello_hip_render_instances_painted(vello_hip_ctx *ctx, const vello_hip_instance *inst, const vello_hip_paint *paints /* nullable */,
+                                       uint32_t n, const vello_hip_render_params *params, void *out_device, size_t out_stride);
 
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a
  * later opaque full-tile cover is normally not emitted; the image is the same, but bump.segments / bump.ptcl and the

@@ -6,9 +6,13 @@ distributions, 30 000 instances, 1600 x 1600, MSAA16 -- with every symbol turnin
 (b) the time of the render_instances call itself, the lanes idle;
 (c) with --mode, one route alone for a profiler run (rocprofv3 --kernel-trace --stats -- python scripts/scene_instances_bench.py
     --mode instances --rounds 1): k_compose_scene's own time against the bound 2 x scene bytes / 8 TB/s.
-profiles/scene_instances.txt quotes its output.
+(d) with --paints, every instance painted (vello_hip_render_instances_painted), the colours changing with the phase: the old route is
+    given the PAINTED bytes, the call is timed painted and not, and a profiler run shows k_compose_scene_painted beside k_compose_scene;
+(e) with --library, another build of libvello_hip.so (an earlier commit's, under ab_tmp/) for a same-session A/B of the unpainted path.
+profiles/scene_instances.txt and profiles/instance_paints.txt quote its output.
 
-    python scripts/scene_instances_bench.py [--steps 200] [--warmup 20] [--rounds 3] [--phases 8] [--mode both|instances|frames]"""
+    python scripts/scene_instances_bench.py [--steps 200] [--warmup 20] [--rounds 3] [--phases 8] [--mode both|instances|frames]
+                                            [--paints] [--library ab_tmp/libvello_hip_B.so]"""
 import argparse
 import ctypes
 import os
@@ -38,9 +42,19 @@ def main():
     ap.add_argument("--phases", type=int, default=8)
     ap.add_argument("--instances", type=int, default=30000)
     ap.add_argument("--mode", choices=["both", "instances", "frames"], default="both")
+    ap.add_argument("--paints", action="store_true", help="paint every instance, the colours changing with the phase")
+    ap.add_argument("--library", help="another build of libvello_hip.so (under ab_tmp/)")
     a = ap.parse_args()
+    if a.library:
+        vello_amd._lib._use_library(os.path.abspath(a.library))
     lib = vello_amd.FragmentLibrary(ip.symbol_fragments())
     lists = [ip.symbol_instances(0x5EED0003, n=a.instances, phase=0.05 * k) for k in range(a.phases)]
+    paints = [None] * a.phases
+    if a.paints:
+        for k in range(a.phases):
+            paints[k] = np.zeros(a.instances, dtype=vello_amd.PAINT_DTYPE)
+            paints[k]["flags"] = 1
+            paints[k]["rgba"] = 0xFF000000 | ((np.arange(a.instances, dtype=np.uint32) * 2654435761 + k * 0x010305) & 0xFFFFFF)
     eng = vello_amd.Engine(device=0, capacities=bench.D2_CAPS)
     lib.upload(eng)
     targets = [torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda:0") for _ in range(4)]
@@ -48,9 +62,9 @@ def main():
     p = eng._params(W, H, WHITE, AaConfig.Msaa16)
     # the frames' composed bytes, as the engine composes them (tests/instance_parity.py holds them to a numpy composition)
     scenes, layouts = [], []
-    for li in lists:
+    for li, pt in zip(lists, paints):
         lay, nbytes = eng.instances_layout(li)
-        eng.render_instances(li, W, H, WHITE, AaConfig.Msaa16, out=targets[0])
+        eng.render_instances(li, W, H, WHITE, AaConfig.Msaa16, out=targets[0], **({"paints": pt} if a.paints else {}))
         r = eng.sync()
         assert r == 0, f"sync {r}: {eng.bump()}"
         scenes.append(eng.read_buffer("scene", np.uint8, nbytes).copy())
@@ -58,13 +72,17 @@ def main():
     want = targets[0].cpu().numpy().copy()
     b = eng.bump()
     print(f"symbol map: {len(lib.fragments)} fragments (library {lib.packed.nbytes} B), {a.instances} instances, composed scene {scenes[0].nbytes} B "
-          f"({scenes[0].nbytes / 1e6:.2f} MB), instance list {lists[0].nbytes} B, table {52 * a.instances + 24} B, lines {b['lines']}, segments {b['segments']}", flush=True)
+          f"({scenes[0].nbytes / 1e6:.2f} MB), instance list {lists[0].nbytes} B, table {(60 if a.paints else 52) * a.instances + 24} B{', every instance painted' if a.paints else ''}, lines {b['lines']}, segments {b['segments']}", flush=True)
     print(f"bound for k_compose_scene: 2 x {scenes[0].nbytes} B / 8 TB/s = {2 * scenes[0].nbytes / 8e12 * 1e6:.2f} us", flush=True)
+
+    def call(li, pt, target):
+        if pt is None:
+            return eng._lib.vello_hip_render_instances(eng._h, li.ctypes.data, len(li), ctypes.byref(p), target.data_ptr(), W * 4)
+        return eng._lib.vello_hip_render_instances_painted(eng._h, li.ctypes.data, pt.ctypes.data, len(li), ctypes.byref(p), target.data_ptr(), W * 4)
 
     def by_instances(nif, n):
         for i in range(n):
-            li = lists[i % a.phases]
-            eng._check(eng._lib.vello_hip_render_instances(eng._h, li.ctypes.data, len(li), ctypes.byref(p), targets[i % nif].data_ptr(), W * 4), "render_instances")
+            eng._check(call(lists[i % a.phases], paints[i % a.phases], targets[i % nif]), "render_instances")
         assert eng.sync() == 0
 
     def by_frames(nif, n):
@@ -88,17 +106,17 @@ def main():
     eng.set_frames_in_flight(1)
     if a.mode != "frames":
         # the call itself, the lane idle
-        ts = []
-        for i in range(60):
-            li = lists[i % a.phases]
+        for label, pts in (("render_instances", [None] * a.phases),) + ((("render_instances_painted", paints),) if a.paints else ()):
+            ts = []
+            for i in range(60):
+                assert eng.sync() == 0
+                t0 = time.perf_counter()
+                r = call(lists[i % a.phases], pts[i % a.phases], targets[0])
+                ts.append(time.perf_counter() - t0)
+                assert r == 0
             assert eng.sync() == 0
-            t0 = time.perf_counter()
-            r = eng._lib.vello_hip_render_instances(eng._h, li.ctypes.data, len(li), ctypes.byref(p), targets[0].data_ptr(), W * 4)
-            ts.append(time.perf_counter() - t0)
-            assert r == 0
-        assert eng.sync() == 0
-        ts = np.array(ts[10:]) * 1e6
-        print(f"render_instances call at {a.instances} instances (lane idle, 50 calls): median {np.median(ts):.0f} us, min {ts.min():.0f} us, max {ts.max():.0f} us", flush=True)
+            ts = np.array(ts[10:]) * 1e6
+            print(f"{label} call at {a.instances} instances (lane idle, 50 calls): median {np.median(ts):.0f} us, min {ts.min():.0f} us, max {ts.max():.0f} us", flush=True)
     # both routes show the same frame
     eng._check(eng._lib.vello_hip_render_frame(eng._h, scenes[-1].ctypes.data, scenes[-1].nbytes, ctypes.byref(layouts[-1]), ctypes.byref(p), None, 0,
                                                targets[1].data_ptr(), W * 4), "render_frame")

@@ -91,6 +91,16 @@ pub struct vello_hip_instance {
     pub transform: [f32; 6],
 }
 
+/// Per-instance paint of `vello_hip_render_instances_painted`: `rgba` is a premultiplied RGBA8 `DrawColor` word, R in the low byte.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vello_hip_paint {
+    pub flags: u32,
+    pub rgba: u32,
+}
+
+pub const VELLO_HIP_PAINT_KEEP: u32 = 0;
+pub const VELLO_HIP_PAINT_SOLID: u32 = 1;
 pub const VELLO_HIP_AA_AREA: u32 = 0;
 pub const VELLO_HIP_AA_MSAA8: u32 = 1;
 pub const VELLO_HIP_AA_MSAA16: u32 = 2;
@@ -123,6 +133,7 @@ unsafe extern "C" {
     pub fn vello_hip_upload_fragments(ctx: *mut vello_hip_ctx, scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, ramps: *const u32, n_ramps: u32, frags: *const vello_hip_fragment, n_frags: u32) -> c_int;
     pub fn vello_hip_instances_layout(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, n: u32, layout_out: *mut vello_hip_layout, scene_len_out: *mut usize) -> c_int;
     pub fn vello_hip_render_instances(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, n: u32, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
+    pub fn vello_hip_render_instances_painted(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, paints: *const vello_hip_paint, n: u32, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_resize_image_atlas(ctx: *mut vello_hip_ctx, width: u32, height: u32) -> c_int;
     pub fn vello_hip_write_image(ctx: *mut vello_hip_ctx, x: u32, y: u32, width: u32, height: u32, rgba8: *const u8, stride: usize) -> c_int;
     pub fn vello_hip_copy_images_device(ctx: *mut vello_hip_ctx, copies: *const vello_hip_image_copy, n: u32, src_stream: *mut c_void) -> c_int;

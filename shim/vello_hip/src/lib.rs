@@ -243,6 +243,20 @@ impl HipRenderer {
         unsafe { vello_hip_grow_pools(self.ctx, demand, core::ptr::null_mut()) == VELLO_HIP_OK }
     }
 
+    /// `vello_hip_render_instances_painted`: a frame composed on the GPU from `(fragment, transform)` pairs of the fragment table
+    /// made resident through `raw()` and `vello_hip_upload_fragments`, instance `i` drawn with `paints[i]` when a paint list is
+    /// given, one per instance (`None`: `vello_hip_render_instances`).  A paint's `rgba` is the premultiplied RGBA8 word a solid brush encodes to
+    /// (`DrawColor`, vello_encoding/src/draw.rs:70-74).  Enqueues the frame into device memory and returns without waiting.
+    pub fn render_instances_painted(&mut self, instances: &[vello_hip_instance], paints: Option<&[vello_hip_paint]>, target: *mut c_void,
+                                    stride: usize, params: &vello_hip_render_params) -> Result<(), Error> {
+        if let Some(p) = paints {
+            assert_eq!(p.len(), instances.len());
+        }
+        let paints_ptr = paints.map_or(core::ptr::null(), |p| p.as_ptr());
+        let rc = unsafe { vello_hip_render_instances_painted(self.ctx, instances.as_ptr(), paints_ptr, instances.len() as u32, params, target, stride) };
+        if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
+    }
+
     pub fn raw(&self) -> *mut vello_hip_ctx {
         self.ctx
     }

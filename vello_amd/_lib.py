@@ -61,6 +61,10 @@ class InstanceStruct(ctypes.Structure):  # vello_hip_instance
     _fields_ = [("fragment", ctypes.c_uint32), ("transform", ctypes.c_float * 6)]
 
 
+class PaintStruct(ctypes.Structure):  # vello_hip_paint
+    _fields_ = [("flags", ctypes.c_uint32), ("rgba", ctypes.c_uint32)]
+
+
 def load_library():
     """Loads the product library; raises (never falls back) when it is missing."""
     global _LIB
@@ -103,6 +107,7 @@ def load_library():
     sig("vello_hip_upload_fragments", i32, [vp, vp, sz, c.POINTER(LayoutStruct), vp, u32, c.POINTER(FragmentStruct), u32])
     sig("vello_hip_instances_layout", i32, [vp, vp, u32, c.POINTER(LayoutStruct), c.POINTER(sz)])
     sig("vello_hip_render_instances", i32, [vp, vp, u32, c.POINTER(RenderParamsStruct), vp, sz])
+    sig("vello_hip_render_instances_painted", i32, [vp, vp, vp, u32, c.POINTER(RenderParamsStruct), vp, sz])
     sig("vello_hip_set_frames_in_flight", i32, [vp, u32])
     sig("vello_hip_resize_image_atlas", i32, [vp, u32, u32])
     sig("vello_hip_write_image", i32, [vp, u32, u32, u32, u32, vp, sz])

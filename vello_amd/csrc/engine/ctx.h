@@ -58,11 +58,13 @@ struct SceneSlot {
     bool composed = false;
 };
 // A fragment of the library as the host keeps it: where its range begins in each stream and how long it is -- in the units of
-// ComposeArgs (bytes for tags, words otherwise) -- and what the composed layout and fine's specialisation need of its draw tags.
+// ComposeArgs (bytes for tags, words otherwise) -- what the composed layout and fine's specialisation need of its draw tags, and
+// where the mask of its colour words lies (vello_hip_render_instances_painted).
 struct FragmentInfo {
     uint32_t begin[6], len[6];
     uint32_t n_clips, info_words;
     bool brushes;
+    uint32_t mask_bit;  // where its colour-word mask begins in ctx::frag_masks' bit array (valid while ctx::have_masks)
 };
 constexpr uint32_t MAX_LANES = 8;
 
@@ -79,7 +81,7 @@ struct Lane {
     DevBuf slice_items, slice_counters, cov;  // coarse -> fine: slices of long tiles, their arrival counters, coverage scratch
     DevBuf heavy_list;                // flatten: tag indices for the heavy code, 4 lists (one u32 per tag each, worst case)
     DevBuf arc_items;                 // flatten: arcs the stroke workgroups leave to the heavy code (64 B per segment, worst case)
-    DevBuf compose_table;             // vello_hip_render_instances: the frame's ComposeArgs::table
+    DevBuf compose_table;             // vello_hip_render_instances: the frame's ComposeArgs::table (+ ComposePaintArgs::paints)
     DevBuf front_sync;                // k_front's grid-barrier counter (zeroed once, when allocated)
     uint32_t front_sync_value = 0;    // ... and its value once every launch enqueued so far has run
     struct EvPair {
@@ -132,6 +134,11 @@ struct vello_hip_ctx {
     std::vector<vk::FragmentInfo> fragments;
     bool have_fragments = false;
     vk::DevBuf frag_table;  // ComposeArgs::frags
+    // the fragments' colour-word masks: [n_frags] bit offsets (ComposePaintArgs::frag_bits), then the bit array (::masks), a bit
+    // per draw-data word of every fragment in the table's order.  Not kept (have_masks false) for a table whose draw-data ranges
+    // add up to 2^32 words or more: such a library takes no paints.
+    vk::DevBuf frag_masks;
+    bool have_masks = false;
     vk::DevBuf atlas;  // persistent image atlas (render.rs:160-176), shared by all lanes
     uint32_t atlas_w = 0, atlas_h = 0;
     std::vector<vk::Lane> lanes;

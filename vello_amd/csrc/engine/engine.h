@@ -265,7 +265,7 @@ void launch_atlas_copy(const AtlasCopyDesc *descs, uint32_t n, uint64_t total, u
 // the packed scene holds them: 0 path tags, 1 path data, 2 draw tags, 3 draw data, 4 transforms, 5 styles.  Every offset is in u32 words
 // but the tag stream's, which are in bytes.
 //   table: [6][n + 1] exclusive prefixes of the instances' lengths per stream -- one stream's offsets are consecutive words, so a
-//          search over them reads one run of memory -- then [n] fragment indices, then [n][6] transforms (COMPOSE_TABLE_WORDS);
+//          search over them reads one run of memory -- then [n] fragment indices, then [n][6] transforms, then -- a painted frame's only -- [n][2] paints (compose_table_words);
 //   frags: [n_frags][6] where each fragment's range begins in the library's stream.
 // The grid is cut per stream (wg_first): a workgroup's chunk of steps x 256 words lies in ONE stream, so it needs one slice of one
 // prefix; the last workgroup writes the 16 words of zero slack behind the scene.
@@ -282,7 +282,19 @@ struct ComposeArgs {
     uint32_t wg_first[7];   // first workgroup of each stream; [6]: the slack's
     uint32_t tag_bytes;     // tags of the composed scene, without the padding
 };
-inline size_t compose_table_words(uint32_t n) { return 6u * ((size_t)n + 1u) + 7u * (size_t)n; }
-void launch_compose_scene(const ComposeArgs &a, hipStream_t s);
+// What the painted form of the kernel (k_compose_scene_painted) is handed besides: a frame with a paint list
+// (vello_hip_render_instances_painted).  An unpainted frame's table, arguments and kernel are what they were before there were paints.
+//   paints:    [n][2] (flags, rgba), the vello_hip_paint list verbatim: the lane's table, behind the transforms;
+//   frag_bits: [n_frags] where each fragment's colour-word mask begins in `masks`, in bits;
+//   masks:     a bit per draw-data word of every fragment, in the order of the table, set where the word is a colour word.
+constexpr uint32_t PAINT_SOLID = 1u;  // VELLO_HIP_PAINT_SOLID of include/vello_hip.h (scenes.hip holds the two to each other)
+struct ComposePaintArgs {
+    const uint32_t *paints;
+    const uint32_t *frag_bits;
+    const uint32_t *masks;
+};
+inline size_t compose_table_words(uint32_t n, bool painted) { return 6u * ((size_t)n + 1u) + (painted ? 9u : 7u) * (size_t)n; }
+// pa == nullptr: the unpainted form
+void launch_compose_scene(const ComposeArgs &a, const ComposePaintArgs *pa, hipStream_t s);
 
 }  // namespace vk

@@ -98,9 +98,15 @@ void launch_view_transforms(const Frame &f, hipStream_t s) {
 //   transforms     word k of an entry needs two words of T and two or three of V: V.T as k_view_transforms computes it;
 //   tags           byte-granular: where the four tags of a word come from one instance, two dword loads and a funnel shift; a word
 //                  that straddles instances (or the stream's end) is put together from byte loads.  Words of the padding are zero.
+// The body is shared by two kernels.  k_compose_scene is the unpainted frame's and takes ComposeArgs alone.  k_compose_scene_painted
+// (vello_hip_render_instances_painted with a paint list) differs on the draw-data stream only: a lane whose instance is painted SOLID
+// tests the colour-word mask bit of the library word it has just loaded -- the fragment's bit offset plus the word's offset in the
+// fragment -- and writes the instance's rgba in the word's place where the bit is set.  The paint's two words and the mask word are
+// loads at the instance's granularity: lanes of one instance read the same addresses.
 constexpr uint32_t COMPOSE_LDS_OFFSETS = COMPOSE_MAX_STEPS * 256u + 2u;
 
-__global__ void __launch_bounds__(256) k_compose_scene(ComposeArgs a) {
+template <bool PAINTED>
+__device__ __forceinline__ void compose_scene(const ComposeArgs &a, const ComposePaintArgs &pa) {
     __shared__ uint32_t s_off[COMPOSE_LDS_OFFSETS];
     __shared__ uint32_t s_ends[2];
     const uint32_t bid = blockIdx.x, tid = threadIdx.x;
@@ -184,14 +190,27 @@ __global__ void __launch_bounds__(256) k_compose_scene(ComposeArgs a) {
             float c = __uint_as_float(v[odd]) * __uint_as_float(t[0]) + __uint_as_float(v[2u + odd]) * __uint_as_float(t[1]);
             if (pair == 2u) c = c + __uint_as_float(v[4u + odd]);
             *d = __float_as_uint(c);
+        } else if (PAINTED && s == 3u) {
+            uint32_t v = a.lib[(size_t)a.src_base[3] + begin + (x - o)];
+            const uint32_t *paint = pa.paints + (size_t)i * 2u;  // (i holds a word: i < n)
+            if (paint[0] == PAINT_SOLID) {
+                const uint32_t bit = pa.frag_bits[frag_of[i]] + (x - o);  // < the masks' bits: the host keeps their sum within u32
+                if ((pa.masks[bit >> 5] >> (bit & 31u)) & 1u) v = paint[1];
+            }
+            *d = v;
         } else {
             *d = a.lib[(size_t)a.src_base[s] + begin + (x - o)];
         }
     }
 }
 
-void launch_compose_scene(const ComposeArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL(k_compose_scene, dim3(a.wg_first[6] + 1u), dim3(256), 0, s, a);
+__global__ void __launch_bounds__(256) k_compose_scene(ComposeArgs a) { compose_scene<false>(a, ComposePaintArgs{}); }
+
+__global__ void __launch_bounds__(256) k_compose_scene_painted(ComposeArgs a, ComposePaintArgs pa) { compose_scene<true>(a, pa); }
+
+void launch_compose_scene(const ComposeArgs &a, const ComposePaintArgs *pa, hipStream_t s) {
+    if (pa) hipLaunchKernelGGL(k_compose_scene_painted, dim3(a.wg_first[6] + 1u), dim3(256), 0, s, a, *pa);
+    else hipLaunchKernelGGL(k_compose_scene, dim3(a.wg_first[6] + 1u), dim3(256), 0, s, a);
 }
 
 }  // namespace vk

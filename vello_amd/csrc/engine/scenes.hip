@@ -78,8 +78,10 @@ int size_slot(vello_hip_ctx *c, SceneSlot &sc, const vello_hip_layout &L, size_t
 }
 
 // One fragment against the host bytes of its (checked) library: the rules of vello_hip_upload_fragments in include/vello_hip.h.
+// `mask` (nullable: no masks are kept) is the bit array of the fragments' colour words so far, `mask_bits` bits long: the fragment's bits
+// are appended, one per word of its draw_data range (vello_hip_render_instances_painted has the rule).
 int check_fragment(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout &L, const vello_hip_fragment &fr,
-                          uint32_t index, FragmentInfo &out) {
+                          uint32_t index, FragmentInfo &out, std::vector<uint32_t> *mask, uint64_t mask_bits) {
     auto refuse = [&](const char *why) {
         c->last_error = "upload_fragments: fragment " + std::to_string(index) + ": " + why;
         return VELLO_HIP_E_INVALID;
@@ -116,9 +118,16 @@ int check_fragment(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, con
     uint64_t draw_data_words = 0, info_words = 0;
     uint32_t clip_tags = 0, depth = 0;
     out.brushes = false;
+    out.mask_bit = (uint32_t)mask_bits;
+    if (mask) mask->resize((size_t)((mask_bits + n_entries[3] + 31u) / 32u), 0u);
     for (uint32_t i = fr.draws[0]; i < fr.draws[1]; i++) {
         const uint32_t t = words[L.draw_tag_base + i];
         if (t != DRAWTAG_FILL_COLOR && t != DRAWTAG_BEGIN_CLIP && t != DRAWTAG_END_CLIP && t != DRAWTAG_NOP) out.brushes = true;
+        // both draw objects hold a DrawColor first (draw.rs:70-74, :175-186); a word past the range belongs to a fragment refused below
+        if (mask && (t == DRAWTAG_FILL_COLOR || t == DRAWTAG_BLURRED_ROUNDED_RECT) && draw_data_words < n_entries[3]) {
+            const uint64_t bit = mask_bits + draw_data_words;
+            (*mask)[(size_t)(bit >> 5)] |= 1u << (bit & 31u);
+        }
         clip_tags += t & 1u;
         draw_data_words += (t >> 2) & 0x7u;
         info_words += (t >> 6) & 0xfu;
@@ -145,13 +154,19 @@ struct ComposePlan {
     bool brushes;
 };
 
-int plan_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, ComposePlan &p) {
+static_assert(PAINT_SOLID == VELLO_HIP_PAINT_SOLID && sizeof(vello_hip_paint) == 8, "ComposePaintArgs::paints is the paint list verbatim");
+
+int plan_instances(vello_hip_ctx *c, const vello_hip_instance *inst, const vello_hip_paint *paints, uint32_t n, ComposePlan &p) {
     if (!c->have_fragments || !c->shared.resident) {
         c->last_error = "no fragment table (vello_hip_upload_fragments)";
         return VELLO_HIP_E_INVALID;
     }
     if (n > 0u && !inst) {
         c->last_error = "instances: inst is NULL";
+        return VELLO_HIP_E_INVALID;
+    }
+    if (paints && !c->have_masks) {
+        c->last_error = "instances: the fragments' draw_data ranges add up to 2^32 words or more: the library takes no paints";
         return VELLO_HIP_E_INVALID;
     }
     uint64_t len[6] = {}, n_clips = 0, info = 0;
@@ -167,6 +182,10 @@ int plan_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n,
                 c->last_error = "instance " + std::to_string(i) + ": the transform has an entry that is not finite";
                 return VELLO_HIP_E_INVALID;
             }
+        if (paints && paints[i].flags != VELLO_HIP_PAINT_KEEP && paints[i].flags != VELLO_HIP_PAINT_SOLID) {
+            c->last_error = "instance " + std::to_string(i) + ": paint flags " + std::to_string(paints[i].flags) + " (VELLO_HIP_PAINT_KEEP or _SOLID)";
+            return VELLO_HIP_E_INVALID;
+        }
         const FragmentInfo &fi = c->fragments[inst[i].fragment];
         for (int s = 0; s < 6; s++) len[s] += fi.len[s];
         n_clips += fi.n_clips;
@@ -255,6 +274,7 @@ int vello_hip_upload_scene(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
     // frames still in flight read the old scene
     if ((r = sync_all(c))) return r;
     c->have_fragments = false;  // (vello_hip_upload_fragments sets its table once the scene is resident)
+    c->have_masks = false;
     c->fragments.clear();
     if ((r = load_slot(c, c->shared, c->lanes[0].stream, scene, scene_len, layout, ramps, n_ramps))) return r;
     for (auto &l : c->lanes) {
@@ -273,6 +293,7 @@ int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t sc
     // whatever goes wrong from here on, nothing stays resident (frames in flight keep what they were enqueued with)
     c->shared.resident = false;
     c->have_fragments = false;
+    c->have_masks = false;
     c->fragments.clear();
     if (n_frags > 0u && !frags) {
         c->last_error = "upload_fragments: frags is NULL";
@@ -281,8 +302,15 @@ int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t sc
     int r;
     if ((r = check_layout(c, scene, scene_len, layout))) return r;
     std::vector<FragmentInfo> infos(n_frags);
-    for (uint32_t i = 0; i < n_frags; i++)
-        if ((r = check_fragment(c, scene, scene_len, *layout, frags[i], i, infos[i]))) return r;
+    // [n_frags] bit offsets, then the colour-word masks (ctx::frag_masks); bit offsets stay within u32 or no masks are kept
+    std::vector<uint32_t> masks;
+    uint64_t mask_bits = 0;
+    bool keep_masks = true;
+    for (uint32_t i = 0; i < n_frags; i++) {
+        if ((r = check_fragment(c, scene, scene_len, *layout, frags[i], i, infos[i], keep_masks ? &masks : nullptr, mask_bits))) return r;
+        mask_bits += infos[i].len[3];
+        if (mask_bits > 0xffffffffull) keep_masks = false, masks = {};
+    }
     if ((r = vello_hip_upload_scene(c, scene, scene_len, layout, ramps, n_ramps))) return r;
     // (the lanes are idle: upload_scene waited for them, so no frame reads the table that ensure() may free)
     std::vector<uint32_t> begins((size_t)n_frags * 6u);
@@ -299,15 +327,33 @@ int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t sc
             return VELLO_HIP_E_HIP;
         }
     }
+    if (keep_masks) {
+        std::vector<uint32_t> block((size_t)n_frags + masks.size());
+        for (uint32_t i = 0; i < n_frags; i++) block[i] = infos[i].mask_bit;
+        if (!masks.empty()) std::memcpy(&block[n_frags], masks.data(), masks.size() * 4u);
+        if ((r = ensure(c, c->frag_masks, block.size() * 4u))) {
+            c->shared.resident = false;
+            return r;
+        }
+        if (!block.empty()) {
+            const hipError_t e = hipMemcpy(c->frag_masks.ptr, block.data(), block.size() * 4u, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                c->shared.resident = false;
+                c->last_error = std::string("upload_fragments: ") + hipGetErrorString(e);
+                return VELLO_HIP_E_HIP;
+            }
+        }
+    }
     c->fragments = std::move(infos);
     c->have_fragments = true;
+    c->have_masks = keep_masks;
     return VELLO_HIP_OK;
 }
 
 int vello_hip_instances_layout(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, vello_hip_layout *layout_out, size_t *scene_len_out) {
     if (!c) return VELLO_HIP_E_INVALID;
     ComposePlan p;
-    if (int r = plan_instances(c, inst, n, p)) return r;
+    if (int r = plan_instances(c, inst, nullptr, n, p)) return r;
     if (layout_out) *layout_out = p.layout;
     if (scene_len_out) *scene_len_out = p.scene_len;
     return VELLO_HIP_OK;
@@ -315,14 +361,16 @@ int vello_hip_instances_layout(vello_hip_ctx *c, const vello_hip_instance *inst,
 
 // vello_hip_render_frame with k_compose_scene in the host copy's place.  Everything that can refuse the frame is asked before the
 // lane is taken; the instance table goes through a pinned block to the lane's own table, on the lane's stream, ahead of the kernel.
-int vello_hip_render_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, const vello_hip_render_params *params, void *out_device,
-                               size_t out_stride) {
+// With a paint list the table carries it behind the transforms and the kernel's painted form runs; without one, the table, the
+// arguments and the kernel are the unpainted frame's.
+int vello_hip_render_instances_painted(vello_hip_ctx *c, const vello_hip_instance *inst, const vello_hip_paint *paints, uint32_t n,
+                                       const vello_hip_render_params *params, void *out_device, size_t out_stride) {
     if (!c || !params) return VELLO_HIP_E_INVALID;
     ComposePlan p;
-    int r = plan_instances(c, inst, n, p);
+    int r = plan_instances(c, inst, paints, n, p);
     if (r) return r;
     if ((r = check_target(c, params, out_device, out_stride, true))) return r;
-    const size_t table_bytes = compose_table_words(n) * 4u;
+    const size_t table_bytes = compose_table_words(n, paints != nullptr) * 4u;
     Staging *st = nullptr;
     const auto set_up = [&](Lane &l, bool &) -> int {
         HIP_TRY(c, hipStreamSynchronize(l.stream));
@@ -362,6 +410,7 @@ int vello_hip_render_instances(vello_hip_ctx *c, const vello_hip_instance *inst,
                 std::memcpy(frag_of + n + (size_t)i * 6u, inst[i].transform, 24);
             }
             for (int s = 0; s < 6; s++) off[s][n] = run[s];
+            if (paints && n) std::memcpy(frag_of + 7u * (size_t)n, paints, (size_t)n * sizeof *paints);
         }
         ComposeArgs a{};
         a.lib = (const uint32_t *)c->shared.scene.ptr;
@@ -390,13 +439,24 @@ int vello_hip_render_instances(vello_hip_ctx *c, const vello_hip_instance *inst,
         HIP_TRY(c, hipMemcpyAsync(l.compose_table.ptr, st->host, table_bytes, hipMemcpyHostToDevice, l.stream));
         HIP_TRY(c, hipEventRecord(st->done, l.stream));
         st->busy = true;
-        launch_compose_scene(a, l.stream);
+        ComposePaintArgs pa{};
+        if (paints) {
+            pa.paints = a.table + 6u * ((size_t)n + 1u) + 7u * (size_t)n;
+            pa.frag_bits = (const uint32_t *)c->frag_masks.ptr;
+            pa.masks = pa.frag_bits + c->fragments.size();
+        }
+        launch_compose_scene(a, paints ? &pa : nullptr, l.stream);
         HIP_TRY(c, hipGetLastError());
         l.own.resident = true;
         return 0;
     };
     // (the rotation moves only once nothing can refuse the frame)
     return enter_frame(c, params, out_device, out_stride, false, VELLO_HIP_STAGE_FINE, set_up, staged, enqueue);
+}
+
+int vello_hip_render_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, const vello_hip_render_params *params, void *out_device,
+                               size_t out_stride) {
+    return vello_hip_render_instances_painted(c, inst, nullptr, n, params, out_device, out_stride);
 }
 
 }  // extern "C"

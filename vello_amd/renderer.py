@@ -7,7 +7,7 @@ import enum
 import numpy as np
 
 from ._lib import (load_library, is_emulated, VelloHipError, Capacities, Bump, LayoutStruct, RenderParamsStruct, ImageCopyStruct, FragmentStruct,
-                   InstanceStruct)
+                   InstanceStruct, PaintStruct)
 from .scene import Color, ImageAlphaType, ImageData, ImageFormat
 
 
@@ -51,6 +51,9 @@ def _view_floats(view):
 
 INSTANCE_DTYPE = np.dtype([("fragment", "<u4"), ("transform", "<f4", (6,))])  # vello_hip_instance, 28 bytes
 assert INSTANCE_DTYPE.itemsize == ctypes.sizeof(InstanceStruct)
+PAINT_DTYPE = np.dtype([("flags", "<u4"), ("rgba", "<u4")])  # vello_hip_paint, 8 bytes
+assert PAINT_DTYPE.itemsize == ctypes.sizeof(PaintStruct)
+PAINT_KEEP, PAINT_SOLID = 0, 1  # VELLO_HIP_PAINT_KEEP / _SOLID
 FRAGMENT_STREAMS = ("path_tags", "path_data", "draws", "draw_data", "transforms", "styles")
 
 
@@ -62,6 +65,18 @@ def instance_array(instances):
     for i, (fragment, transform) in enumerate(instances):
         out[i]["fragment"] = int(fragment)
         out[i]["transform"] = [float(v) for v in (transform.c if hasattr(transform, "c") else transform)]
+    return out
+
+
+def paint_array(paints):
+    """A PAINT_DTYPE array of per-instance paints: None keeps the library's colours, an int is a premultiplied RGBA8 word (R in the
+    low byte, as base_color), a Color is quantised as the encoder quantises a solid brush (Color.premul_rgba8)."""
+    if isinstance(paints, np.ndarray) and paints.dtype == PAINT_DTYPE:
+        return np.ascontiguousarray(paints)
+    out = np.zeros(len(paints), dtype=PAINT_DTYPE)
+    for i, paint in enumerate(paints):
+        if paint is not None:
+            out[i] = (PAINT_SOLID, paint.premul_rgba8() if isinstance(paint, Color) else int(paint))
     return out
 
 
@@ -422,15 +437,25 @@ class Engine:
                     "instances_layout")
         return Layout(*[getattr(lay, k) for k, _ in LayoutStruct._fields_]), int(n.value)
 
-    def render_instances(self, instances, width, height, base_color, aa, out=None, out_stride=None):
+    def render_instances(self, instances, width, height, base_color, aa, out=None, out_stride=None, paints=None):
         """vello_hip_render_instances: composes this frame's scene on the GPU from `instances` -- (fragment index, transform) pairs
-        or an INSTANCE_DTYPE array -- of the fragments of upload_fragments, and enqueues the frame like render_frame."""
+        or an INSTANCE_DTYPE array -- of the fragments of upload_fragments, and enqueues the frame like render_frame.  With `paints`
+        (what paint_array takes, one entry per instance) it is vello_hip_render_instances_painted: the colour words of every instance
+        with a paint become that paint."""
         inst = instance_array(instances)
         p = self._params(width, height, base_color, aa)
         ptr, stride = None, 0
         if out is not None:
             ptr, stride, _ = _target(self._lib, out, width, height, device_only=True, stride=out_stride)
-        self._check(self._lib.vello_hip_render_instances(self._h, inst.ctypes.data, len(inst), ctypes.byref(p), ptr, stride), "render_instances")
+        if paints is None:
+            self._check(self._lib.vello_hip_render_instances(self._h, inst.ctypes.data, len(inst), ctypes.byref(p), ptr, stride), "render_instances")
+            return
+        pt = paint_array(paints)
+        if len(pt) != len(inst):
+            raise ValueError(f"{len(pt)} paints for {len(inst)} instances")
+        # (an empty numpy array still has an address: n == 0 with a paint list is a call with a non-null pointer)
+        self._check(self._lib.vello_hip_render_instances_painted(self._h, inst.ctypes.data, pt.ctypes.data, len(inst), ctypes.byref(p), ptr, stride),
+                    "render_instances_painted")
 
     def render_resident(self, width, height, base_color, aa, out=None, out_stride=None):
         """vello_hip_render_resident.  `out`: a dense uint8 target of height * width * 4 bytes, or an [H, W, 4] view whose rows lie
