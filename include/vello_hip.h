@@ -27,6 +27,10 @@
  *   vello_hip_render_instances    per instance + resolve + upload        vello_encoding/src/encoding.rs:95-152
  *   vello_hip_render_instances_painted  ... each appended scene encoded  vello_encoding/src/encoding.rs:280-290
  *                              with a solid brush of its own (encode_brush)
+ *   vello_hip_retain_instances /  the same Scene::append per pair, hoisted  vello/src/scene.rs (append),
+ *   vello_hip_render_retained /   out of the frame loop: the composed scene  vello_encoding/src/encoding.rs:95-152,
+ *   vello_hip_release_retained    is kept, a frame brings only the          vello_encoding/src/math.rs:51-73
+ *                              transforms of its appends (Transform::mul)
  *   vello_hip_sync             queue.submit + device.poll                vello/src/wgpu_engine.rs:757
  *   vello_hip_set_frames_in_flight  back-to-back queue.submit without waiting  vello/src/wgpu_engine.rs:757
  *   vello_hip_get_bump         the robust path's bump download           vello/src/lib.rs:730, :753-761
@@ -411,6 +415,56 @@ typedef struct vello_hip_paint {
  * pool estimation for instance lists, which stays where vello_hip_render_instances left it. */
 int vello_hip_render_instances_painted(vello_hip_ctx *ctx, const vello_hip_instance *inst, const vello_hip_paint *paints /* nullable */,
                                        uint32_t n, const vello_hip_render_params *params, void *out_device, size_t out_stride);
+
+/* Retained instance lists: the list that the previous frame drew, re-posed.  The reference seam is still
+ * Scene::append(&fragment, Some(transform)) per pair; this is the same composed scene with the appends hoisted out of the frame
+ * loop.  vello_hip_retain_instances composes `inst` (with `paints`, nullable) ONCE into a retained scene owned by the context;
+ * vello_hip_render_retained enqueues one frame of it under this frame's poses -- one 6-float transform per instance, which take
+ * the place of inst[i].transform -- and returns without waiting.
+ *   1. WHAT IS RETAINED.  The scene vello_hip_render_instances_painted(inst, paints, n) documents -- layout, length, padding, slack
+ *      and rule 1b's colour words -- except that every transform entry is the library's T VERBATIM (copied, not multiplied by an
+ *      identity: 1 * -0 + 0 * x is +0).  It lives in a slot of its own beside the resident library and the buffer sets' private
+ *      slots; ramps and atlas are the library's.  Resident with it: for every transform entry the instance that owns it, and the
+ *      rest poses inst[i].transform.  Every refusal of vello_hip_render_instances_painted applies, and a list of more than 2^32 / 6
+ *      instances is refused as well: VELLO_HIP_E_INVALID with nothing retained and a previously retained list left as it was.  The
+ *      call waits for the frames in flight, as an upload does; a second call replaces the list.  vello_hip_upload_scene,
+ *      vello_hip_render's upload and vello_hip_upload_fragments drop the list with the fragment table;
+ *      vello_hip_release_retained frees it (VELLO_HIP_OK when there is none).
+ *   2. A RETAINED FRAME under poses X is, bit for bit in every buffer and counter, the frame
+ *      vello_hip_render_instances_painted((fragment_i, X_i), paints, n) enqueues -- view transform and viewport culling included:
+ *      a transform entry ends up as View.(X_i.T), each product rounded to six f32 words by vello_hip_set_view_transform's formula
+ *      before the next is formed.  ONE kernel (k_instance_transforms, a lane per transform entry) writes the frame's transform
+ *      words into a per-buffer-set copy behind the retained bytes; nothing is re-encoded and no other word is rewritten.  The one
+ *      exception is VELLO_HIP_BUF_SCENE, which shows the retained bytes of rule 1 (the library's T's), as a viewed scene shows
+ *      its own bytes; VELLO_HIP_BUF_CONFIG holds the composed layout.  vello_hip_run_stages after a retained frame acts on the
+ *      retained scene and goes on from that frame's composed transform words as they are (the poses are not read again, and a
+ *      view set since is not applied); on a buffer set that holds none of this list it uses the rest poses.
+ *   3. WHERE THE POSES COME FROM.  transforms == NULL: the rest poses -- a static list re-rendered, or viewed under a moving
+ *      vello_hip_set_view_transform, with no per-instance work on the host.  Host memory (transforms_is_device == 0): n x 6 floats,
+ *      copied through pinned memory during the call (24 bytes per instance; `transforms` may be reused on return); a NaN or
+ *      infinite entry is VELLO_HIP_E_INVALID with vello_hip_last_error naming the instance; src_stream must be NULL.  Device
+ *      memory (transforms_is_device != 0): 4-byte aligned, n x 6 floats in one allocation on the context's device (anything else is
+ *      refused in GPU builds, as vello_hip_copy_images_device refuses it).  The host does no per-instance work and does not
+ *      read the poses.  With `src_stream` (a hipStream_t) the frame waits for what has been enqueued on it so far, and src_stream
+ *      then waits for the kernel that reads the poses: work enqueued there afterwards may overwrite them.  Nothing waits on the
+ *      host.  Without src_stream the caller keeps the poses valid and unchanged until the frame has finished.  A device pose with
+ *      a NaN or infinite entry is found by the kernel: the frame is discarded like one whose tag stream contradicts its scene --
+ *      the target untouched, VELLO_HIP_E_INVALID at vello_hip_sync -- and the next frame is unaffected.
+ *   4. Poses belong to their frame: four frames in flight may show four pose sets of one retained list in four targets.
+ *      Retained frames rotate over the in-flight buffer sets with every other kind of frame and may alternate with
+ *      vello_hip_render_resident, _render_frame and _render_instances frames.  No frame modifies the library's bytes or the
+ *      retained bytes.  THE TARGET (at vello_hip_render_resident) applies.  A pool overflow is reported as for
+ *      vello_hip_render_instances: VELLO_HIP_E_CAPACITY at vello_hip_sync, then vello_hip_grow_pools and a second call.  A
+ *      refused frame (VELLO_HIP_E_INVALID: no retained list, a pose or a pose source as rule 3 refuses it, a target or render
+ *      parameters that are refused) enqueues nothing and leaves the rotation where it was.
+ *   5. Out of scope: per-frame paints (colour words sit in draw data, which has no per-frame copy: retain again); per-frame
+ *      changes of membership or order (retain again); pool estimation for instance lists; more than one retained list per
+ *      context. */
+int vello_hip_retain_instances(vello_hip_ctx *ctx, const vello_hip_instance *inst, const vello_hip_paint *paints /* nullable */, uint32_t n);
+int vello_hip_render_retained(vello_hip_ctx *ctx, const float *transforms /* n x 6, nullable */, int transforms_is_device,
+                              void *src_stream /* nullable hipStream_t */, const vello_hip_render_params *params, void *out_device,
+                              size_t out_stride);
+int vello_hip_release_retained(vello_hip_ctx *ctx);
 
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a
  * later opaque full-tile cover is normally not emitted; the image is the same, but bump.segments / bump.ptcl and the

@@ -134,6 +134,9 @@ unsafe extern "C" {
     pub fn vello_hip_instances_layout(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, n: u32, layout_out: *mut vello_hip_layout, scene_len_out: *mut usize) -> c_int;
     pub fn vello_hip_render_instances(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, n: u32, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_render_instances_painted(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, paints: *const vello_hip_paint, n: u32, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
+    pub fn vello_hip_retain_instances(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, paints: *const vello_hip_paint, n: u32) -> c_int;
+    pub fn vello_hip_render_retained(ctx: *mut vello_hip_ctx, transforms: *const f32, transforms_is_device: c_int, src_stream: *mut c_void, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
+    pub fn vello_hip_release_retained(ctx: *mut vello_hip_ctx) -> c_int;
     pub fn vello_hip_resize_image_atlas(ctx: *mut vello_hip_ctx, width: u32, height: u32) -> c_int;
     pub fn vello_hip_write_image(ctx: *mut vello_hip_ctx, x: u32, y: u32, width: u32, height: u32, rgba8: *const u8, stride: usize) -> c_int;
     pub fn vello_hip_copy_images_device(ctx: *mut vello_hip_ctx, copies: *const vello_hip_image_copy, n: u32, src_stream: *mut c_void) -> c_int;

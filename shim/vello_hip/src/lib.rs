@@ -257,6 +257,41 @@ impl HipRenderer {
         if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
     }
 
+    /// `vello_hip_retain_instances`: composes the list once into the context's retained scene; `render_retained` then re-poses it per
+    /// frame.  Waits for the frames in flight.
+    pub fn retain_instances(&mut self, instances: &[vello_hip_instance], paints: Option<&[vello_hip_paint]>) -> Result<(), Error> {
+        if let Some(p) = paints {
+            assert_eq!(p.len(), instances.len());
+        }
+        let paints_ptr = paints.map_or(core::ptr::null(), |p| p.as_ptr());
+        let rc = unsafe { vello_hip_retain_instances(self.ctx, instances.as_ptr(), paints_ptr, instances.len() as u32) };
+        if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
+    }
+
+    /// `vello_hip_render_retained` with poses in host memory, one `[m0 m1 m2 m3 t0 t1]` per retained instance (`None`: the rest
+    /// poses).  Enqueues the frame into device memory and returns without waiting.
+    pub fn render_retained(&mut self, poses: Option<&[[f32; 6]]>, target: *mut c_void, stride: usize, params: &vello_hip_render_params) -> Result<(), Error> {
+        let poses_ptr = poses.map_or(core::ptr::null(), |p| p.as_ptr().cast::<f32>());
+        let rc = unsafe { vello_hip_render_retained(self.ctx, poses_ptr, 0, core::ptr::null_mut(), params, target, stride) };
+        if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
+    }
+
+    /// `vello_hip_render_retained` with poses in device memory (`6 * n` floats on the context's device, 4-byte aligned), written by
+    /// work on `src_stream` (a `hipStream_t`, nullable): the frame waits for that work, the stream for the kernel that reads them.
+    ///
+    /// # Safety
+    /// `poses` must stay valid, and unchanged by anything but `src_stream`, until the frame has read it.
+    pub unsafe fn render_retained_device(&mut self, poses: *const f32, src_stream: *mut c_void, target: *mut c_void, stride: usize,
+                                         params: &vello_hip_render_params) -> Result<(), Error> {
+        let rc = vello_hip_render_retained(self.ctx, poses, 1, src_stream, params, target, stride);
+        if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
+    }
+
+    /// `vello_hip_release_retained`.
+    pub fn release_retained(&mut self) -> bool {
+        unsafe { vello_hip_release_retained(self.ctx) == VELLO_HIP_OK }
+    }
+
     pub fn raw(&self) -> *mut vello_hip_ctx {
         self.ctx
     }

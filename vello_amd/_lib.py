@@ -108,6 +108,9 @@ def load_library():
     sig("vello_hip_instances_layout", i32, [vp, vp, u32, c.POINTER(LayoutStruct), c.POINTER(sz)])
     sig("vello_hip_render_instances", i32, [vp, vp, u32, c.POINTER(RenderParamsStruct), vp, sz])
     sig("vello_hip_render_instances_painted", i32, [vp, vp, vp, u32, c.POINTER(RenderParamsStruct), vp, sz])
+    sig("vello_hip_retain_instances", i32, [vp, vp, vp, u32])
+    sig("vello_hip_render_retained", i32, [vp, vp, i32, vp, c.POINTER(RenderParamsStruct), vp, sz])
+    sig("vello_hip_release_retained", i32, [vp])
     sig("vello_hip_set_frames_in_flight", i32, [vp, u32])
     sig("vello_hip_resize_image_atlas", i32, [vp, u32, u32])
     sig("vello_hip_write_image", i32, [vp, u32, u32, u32, u32, vp, sz])

@@ -296,6 +296,7 @@ void vello_hip_destroy(vello_hip_ctx *c) {
         (void)hipEventDestroy(c->lane_mark);
         (void)hipStreamDestroy(c->upload_stream);
     }
+    if (c->pose_mark) (void)hipEventDestroy(c->pose_mark);
     if (c->frame_done) (void)hipEventDestroy(c->frame_done);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     delete c;
@@ -319,6 +320,7 @@ int vello_hip_set_frames_in_flight(vello_hip_ctx *c, uint32_t n) {
         // slice items a frame of the scene was seen to ask for say nothing about the other mode -- unknown again (the default
         // capacity, and the next finished frame is read back)
         c->shared.slice_demand = -1;
+        c->retained.slice_demand = -1;
         for (auto &l : c->lanes) l.own.slice_demand = -1;
     }
     c->n_active = n;  // shrinking keeps the extra lanes' buffers; only the rotation changes

@@ -54,7 +54,8 @@ struct SceneSlot {
     size_t view_at = 0;
     size_t view_cap_bytes = 0;  // bytes allocated from view_at on (ensure_scene)
     uint32_t view_sets = 0, view_set_words = 0;
-    // the bytes were composed from the library's fragments (vello_hip_render_instances): ramps are the shared slot's
+    // the bytes were composed from the library's fragments (vello_hip_render_instances, vello_hip_retain_instances): ramps are the
+    // shared slot's
     bool composed = false;
 };
 // A fragment of the library as the host keeps it: where its range begins in each stream and how long it is -- in the units of
@@ -68,10 +69,14 @@ struct FragmentInfo {
 };
 constexpr uint32_t MAX_LANES = 8;
 
+// Which scene a lane's latest frame reads (slot_of): the context's shared scene (vello_hip_upload_scene), the lane's private slot
+// (vello_hip_render_frame, vello_hip_render_instances) or the context's retained instance list (vello_hip_retain_instances).
+enum class LaneScene : uint8_t { Shared, Own, Retained };
+
 struct Lane {
     hipStream_t stream = nullptr;
     SceneSlot own;          // vello_hip_render_frame: the scene of the frame this lane is rendering
-    bool use_own = false;   // else the context's shared scene (vello_hip_upload_scene)
+    LaneScene which = LaneScene::Shared;
     DevBuf buf[VELLO_HIP_BUF_COUNT];  // SCENE / CONFIG / BUMP entries unused (shared, see ctx; the head of zero_region: find_buf)
     DevBuf zero_region;               // Control + look-back states
     DevBuf clip_stack;
@@ -82,6 +87,17 @@ struct Lane {
     DevBuf heavy_list;                // flatten: tag indices for the heavy code, 4 lists (one u32 per tag each, worst case)
     DevBuf arc_items;                 // flatten: arcs the stroke workgroups leave to the heavy code (64 B per segment, worst case)
     DevBuf compose_table;             // vello_hip_render_instances: the frame's ComposeArgs::table (+ ComposePaintArgs::paints)
+    // vello_hip_render_retained: the frame's poses when they came from the host (n x 6 words, copied on the lane's stream) ...
+    DevBuf poses;
+    // ... and where the frame's k_instance_transforms reads them: `poses`, the caller's device memory, or null for the rest poses
+    const uint32_t *pose_src = nullptr;
+    hipStream_t pose_stream = nullptr;  // the caller's stream that waits for that kernel (null: none)
+    bool pose_check = false;            // the caller's device memory: the host has not seen the poses, the kernel tests them
+    // (all three belong to the frame being entered: vello_hip_render_retained clears them before it returns, so that no later
+    // frame of the lane reads the caller's memory or stream again)
+    // ctx::retained.generation of the list whose composed transform words the lane's copy holds (0: none): vello_hip_run_stages
+    // after a retained frame goes on from them
+    uint64_t posed_generation = 0;
     DevBuf front_sync;                // k_front's grid-barrier counter (zeroed once, when allocated)
     uint32_t front_sync_value = 0;    // ... and its value once every launch enqueued so far has run
     struct EvPair {
@@ -139,6 +155,14 @@ struct vello_hip_ctx {
     // add up to 2^32 words or more: such a library takes no paints.
     vk::DevBuf frag_masks;
     bool have_masks = false;
+    // vello_hip_retain_instances: the composed scene of ONE instance list, kept across frames (transform entries: the library's,
+    // verbatim; a transform copy per lane behind its bytes, as the shared slot has), the instance that owns each transform entry
+    // ([n_xf] u32) and the rest poses ([n][6] f32).  Dropped with the fragment table.
+    vk::SceneSlot retained;
+    vk::DevBuf retained_owner, retained_rest;
+    uint32_t retained_n = 0;
+    bool have_retained = false;
+    hipEvent_t pose_mark = nullptr;  // orders a retained frame's pose kernel against the caller's src_stream
     vk::DevBuf atlas;  // persistent image atlas (render.rs:160-176), shared by all lanes
     uint32_t atlas_w = 0, atlas_h = 0;
     std::vector<vk::Lane> lanes;
@@ -188,7 +212,9 @@ namespace vk {
         }                                                                                              \
     } while (0)
 
-inline SceneSlot &slot_of(vello_hip_ctx *c, Lane &l) { return l.use_own ? l.own : c->shared; }
+inline SceneSlot &slot_of(vello_hip_ctx *c, Lane &l) {
+    return l.which == LaneScene::Own ? l.own : l.which == LaneScene::Retained ? c->retained : c->shared;
+}
 // bytes between the rows of a target
 inline size_t row_stride(const vello_hip_render_params *p, size_t out_stride) { return out_stride ? out_stride : (size_t)p->width * 4u; }
 
@@ -207,6 +233,7 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
 // scenes.hip
 int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
               const uint32_t *ramps, uint32_t n_ramps);
+void drop_retained(vello_hip_ctx *c);
 // atlas.hip
 int acquire_staging(vello_hip_ctx *c, size_t bytes, Staging *&out);
 // seams.hip
@@ -215,9 +242,9 @@ hipEvent_t get_event(vello_hip_ctx *c);
 // One step of enter_frame that an entry point has nothing to add to.
 constexpr auto no_step = [](Lane &) { return 0; };
 
-// How vello_hip_render_frame, vello_hip_render_instances and vello_hip_render_resident enqueue a frame on the next lane of the
+// How vello_hip_render_frame, vello_hip_render_instances, vello_hip_render_retained and vello_hip_render_resident enqueue a frame on the next lane of the
 // rotation; each hands in what it does differently:
-//   set_up(l, new_scene)   waits for the lane where it must and gives it its scene slot (l.use_own); new_scene = false where the
+//   set_up(l, new_scene)   waits for the lane where it must and gives it its scene slot (l.which); new_scene = false where the
 //                          lane's scene-dependent buffers already fit the slot
 //   rotate_first           the rotation moves before prepare_frame (a frame that prepare_frame refuses has then moved it) or only
 //                          once prepare_frame has accepted the frame
@@ -234,10 +261,19 @@ int enter_frame(vello_hip_ctx *c, const vello_hip_render_params *params, void *o
     Lane &l = c->lanes[li];
     int r;
     bool new_scene = true;
+    const LaneScene was = l.which;
     if ((r = set_up(l, new_scene))) return r;
-    if (new_scene && (r = alloc_lane_scene(c, l, slot_of(c, l)))) return r;
+    if (new_scene && (r = alloc_lane_scene(c, l, slot_of(c, l)))) {
+        // the lane is not sized for its new slot (buffers only ever grow: it still fits the one it had): the next frame of this
+        // slot must see new_scene again
+        l.which = was;
+        return r;
+    }
     uint32_t xf_base;
-    if (c->has_view && (l.use_own || c->shared.resident) && (r = view_base(c, slot_of(c, l), l, xf_base))) return r;
+    // (a retained frame always reads its lane's copy, view or no view)
+    if ((c->has_view || l.which == LaneScene::Retained) && (l.which != LaneScene::Shared || c->shared.resident) &&
+        (r = view_base(c, slot_of(c, l), l, xf_base)))
+        return r;
     if ((r = staged(l))) return r;
     const auto rotate = [&] {
         c->next_lane = (li + 1u) % c->n_active;
@@ -246,7 +282,7 @@ int enter_frame(vello_hip_ctx *c, const vello_hip_render_params *params, void *o
     if (rotate_first) rotate();
     Frame f;
     if ((r = prepare_frame(c, l, params, out_device, out_stride, f, false))) {
-        if (slot_of(c, l).composed) slot_of(c, l).resident = false;
+        if (l.which == LaneScene::Own && l.own.composed) l.own.resident = false;
         return r;
     }
     if (!rotate_first) rotate();

@@ -151,6 +151,18 @@ struct Frame {
     uint32_t xf_base;
     bool has_view;
     Xform view;
+    // A frame of the retained instance list (vello_hip_render_retained): xf_base is ALWAYS the lane's copy, which k_instance_transforms
+    // fills at the head of the frame from the list's owner table and this frame's poses (pose_words; null: the copy already holds
+    // the frame's words, nothing is launched -- vello_hip_run_stages after a retained frame).  pose_stream (nullable) is the
+    // caller's stream that waits for that kernel; pose_mark the event it does so through.  pose_check: the poses are the caller's
+    // device memory, which the host has not read -- the kernel tests them (host poses and the rest poses were tested on the host).
+    bool retained;
+    const uint32_t *xf_owner;
+    const uint32_t *pose_words;
+    uint32_t n_instances;
+    hipStream_t pose_stream;
+    hipEvent_t pose_mark;
+    bool pose_check;
     Control *control;
     uint32_t *heavy_list;   // flatten: tag indices that need the Euler-spiral / stroker path
     uint32_t *arc_items;    // flatten: 16 words per round join / cap arc that a stroke workgroup leaves to the heavy code
@@ -210,6 +222,21 @@ inline Config xf_config(const Frame &f) {
 }
 // k_view_transforms (scene_ops.hip): fills the frame's composed transform words; launched at the head of a frame that has a view
 void launch_view_transforms(const Frame &f, hipStream_t s);
+// k_instance_transforms (scene_ops.hip): what it is handed by value.  Slot 0 of `out` is the six words below the retained scene's
+// transform stream, slots 1 .. n_xf are X_owner(e).T_e, with View in front when has_view is set: the frame's composed transform words.
+struct InstanceXfArgs {
+    const uint32_t *scene;   // the retained scene: its transform entries are the library's, verbatim
+    const uint32_t *owner;   // [n_xf] the instance that owns each transform entry (non-decreasing)
+    const uint32_t *poses;   // [n][6] this frame's poses, 4-byte aligned
+    uint32_t *out;           // slot 0 of the lane's copy
+    uint32_t *failed;        // nullable: &control->bump.failed, ORed with FAILED_SCENE when a pose holds a NaN or an infinity
+    uint32_t transform_base, n_xf, n;
+    uint32_t has_view;
+    Xform view;
+};
+// fills the composed transform words of a retained frame; check_poses: the frame's control block has been cleared on `s` and the
+// pathtag scan has not been enqueued yet
+void launch_instance_transforms(const Frame &f, bool check_poses, hipStream_t s);
 
 void launch_pathtag_scan(const Frame &f, hipStream_t s);
 // (mid: when not null, an event is recorded behind every kernel of the stage but the last: per-KERNEL times of a stage of

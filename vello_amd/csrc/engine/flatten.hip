@@ -1945,10 +1945,11 @@ uint32_t launch_front(const Frame &f, hipStream_t s, uint32_t stages, bool with_
         for (uint32_t b = st; b != 0u; b &= b - 1u) n++;
         return n_wg == 1u ? 0u : n_wg * (n - 1u);
     };
-    // A frame with a view (Frame::has_view): the pathtag scan judges the tag stream against the scene's own layout, the stages
-    // behind it read the composed transform words through theirs (xf_config) -- two launches of the same kernel, cut behind the scan
+    // A frame whose transform words are a composed copy (one with a view, Frame::has_view, or of the retained instance list,
+    // Frame::retained): the pathtag scan judges the tag stream against the scene's own layout, the stages behind it read the
+    // composed words through theirs (xf_config) -- two launches of the same kernel, cut behind the scan
     const uint32_t scan_part = FRONT_ZERO | FRONT_PATHTAG;
-    if (f.has_view && (stages & FRONT_PATHTAG) != 0u && (stages & ~scan_part) != 0u) {
+    if ((f.has_view || f.retained) && (stages & FRONT_PATHTAG) != 0u && (stages & ~scan_part) != 0u) {
         FrontArgs a0 = a, a1 = a;
         a0.stages = stages & scan_part;
         a1.stages = stages & ~scan_part;

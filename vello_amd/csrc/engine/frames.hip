@@ -121,7 +121,7 @@ namespace vk {
 // the copy: slot -1 comes first).  VELLO_HIP_E_INVALID for a scene so large that the copy is out of a u32 offset's reach.  The entry
 // points that rotate the lanes ask before they rotate, so that a refused frame leaves the rotation where it was.
 int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base) {
-    const size_t set = l.use_own ? 0u : (size_t)(&l - c->lanes.data());
+    const size_t set = l.which == LaneScene::Own ? 0u : (size_t)(&l - c->lanes.data());
     const uint64_t at = (uint64_t)sc.view_at + (uint64_t)set * sc.view_set_words + 6u;
     if (set >= sc.view_sets || at + sc.view_set_words > 0xffffffffull) {
         c->last_error = "the scene is too large for a view transform (its transform words must lie within 2^32 words of its start)";
@@ -207,7 +207,16 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
     f.has_view = c->has_view;
     f.view = c->view;
     f.xf_base = sc.layout.transform_base;
-    if (f.has_view && (r = view_base(c, sc, l, f.xf_base))) return r;
+    // a frame of the retained list reads its lane's copy whether a view is set or not; its poses are the lane's (the entry point
+    // has set them; vello_hip_run_stages picks its own)
+    f.retained = &sc == &c->retained;
+    if ((f.has_view || f.retained) && (r = view_base(c, sc, l, f.xf_base))) return r;
+    f.xf_owner = f.retained ? (const uint32_t *)c->retained_owner.ptr : nullptr;
+    f.pose_words = f.retained ? (l.pose_src ? l.pose_src : (const uint32_t *)c->retained_rest.ptr) : nullptr;
+    f.n_instances = f.retained ? c->retained_n : 0u;
+    f.pose_stream = f.retained ? l.pose_stream : nullptr;
+    f.pose_mark = c->pose_mark;
+    f.pose_check = f.retained && l.pose_check;
     f.control = (Control *)l.zero_region.ptr;
     f.zero_bytes = (uint32_t)sc.zero_bytes;
     f.front_sync = (uint32_t *)l.front_sync.ptr;
@@ -327,10 +336,29 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
                    flatten_n_seg_max(f) <= FRONT_TINY_SEGMENTS && f.flatten_coop && f.stroke_kernel_min_lines != 0u;
     }
     // a frame with a view: its transform words first (outside every stage's events), when the range holds a stage that reads them
-    if (f.has_view && first <= VELLO_HIP_STAGE_DRAW_SCAN && last >= VELLO_HIP_STAGE_FLATTEN) {
+    if (f.has_view && !f.retained && first <= VELLO_HIP_STAGE_DRAW_SCAN && last >= VELLO_HIP_STAGE_FLATTEN) {
         launch_view_transforms(f, st);
         HIP_TRY(c, hipGetLastError());
     }
+    // A frame of the retained list: k_instance_transforms in that kernel's place, view or no view.  Where the poses are the caller's
+    // device memory (pose_check; such a frame begins with the pathtag scan) the frame's zero fill comes first, here instead of in
+    // that stage, so that the kernel can raise FAILED_SCENE over a pose that is not finite: behind the fill, ahead of the scan
+    // (`zeroed`: the stage then neither clears nor has k_front clear).  Poses the host has tested keep the stage's own fill.
+    bool zeroed = false;
+    if (f.retained && f.pose_words && first <= VELLO_HIP_STAGE_DRAW_SCAN && last >= VELLO_HIP_STAGE_FLATTEN) {
+        if (f.pose_check && first == VELLO_HIP_STAGE_PATHTAG_SCAN) {
+            HIP_TRY(c, hipMemsetAsync(l.zero_region.ptr, 0, slot_of(c, l).zero_bytes, st));
+            zeroed = true;
+        }
+        launch_instance_transforms(f, zeroed, st);
+        HIP_TRY(c, hipGetLastError());
+        l.posed_generation = c->retained.generation;
+        if (f.pose_stream) {  // the caller's stream may overwrite the poses once this kernel has read them
+            HIP_TRY(c, hipEventRecord(f.pose_mark, st));
+            HIP_TRY(c, hipStreamWaitEvent(f.pose_stream, f.pose_mark, 0));
+        }
+    }
+    const uint32_t front_zero = zeroed ? 0u : FRONT_ZERO;
     for (int s = first; s <= last; s++) {
         bool prof = ((c->prof_mask >> s) & 1u) != 0u;
         uint32_t front_add = 0u;  // what a k_front launch of this stage adds to the lane's barrier counter (0: one workgroup)
@@ -348,12 +376,12 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
             // render.rs:313 clears `bump`; the same memset resets both look-back states and tickets
             l.flatten_ran = false;
             if (fuse_all) {
-                front_add = launch_front(f, st, FRONT_ZERO | FRONT_PATHTAG | FRONT_LIGHT | FRONT_HEAVY | FRONT_BINNING | FRONT_TILE_ALLOC, true, l.front_sync_value);
+                front_add = launch_front(f, st, front_zero | FRONT_PATHTAG | FRONT_LIGHT | FRONT_HEAVY | FRONT_BINNING | FRONT_TILE_ALLOC, true, l.front_sync_value);
                 front_launched = true;
                 break;
             }
             if (fuse_a) break;  // (with FLATTEN's first launch)
-            HIP_TRY(c, hipMemsetAsync(l.zero_region.ptr, 0, slot_of(c, l).zero_bytes, st));
+            if (!zeroed) HIP_TRY(c, hipMemsetAsync(l.zero_region.ptr, 0, slot_of(c, l).zero_bytes, st));
             launch_pathtag_scan(f, st);
             break;
         case VELLO_HIP_STAGE_FLATTEN:
@@ -362,7 +390,7 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
             // (a range that goes on to DRAW_SCAN: that stage's workgroups ride in flatten's first launch)
             if (fuse_a) {
                 // (k_front's barrier counter advances on the host only once the launch was accepted: ADVICE r5)
-                const uint32_t add = launch_front(f, st, FRONT_ZERO | FRONT_PATHTAG | FRONT_LIGHT, last >= VELLO_HIP_STAGE_DRAW_SCAN, l.front_sync_value);
+                const uint32_t add = launch_front(f, st, front_zero | FRONT_PATHTAG | FRONT_LIGHT, last >= VELLO_HIP_STAGE_DRAW_SCAN, l.front_sync_value);
                 if (int r = front_accepted(c, l, st, add)) return r;
             }
             launch_flatten(f, st, prof ? ev.mid : nullptr, last >= VELLO_HIP_STAGE_DRAW_SCAN, fuse_a);
@@ -422,7 +450,7 @@ int vello_hip_render_frame(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
     const auto set_up = [&](Lane &l, bool &) -> int {
         HIP_TRY(c, hipStreamSynchronize(l.stream));
         if (int r = load_slot(c, l.own, l.stream, scene, scene_len, layout, ramps, n_ramps)) return r;
-        l.use_own = true;
+        l.which = LaneScene::Own;
         return 0;
     };
     return enter_frame(c, params, out_device, out_stride, true, VELLO_HIP_STAGE_FINE, set_up, no_step, no_step);
@@ -432,21 +460,108 @@ int vello_hip_render_resident(vello_hip_ctx *c, const vello_hip_render_params *p
     if (!c) return VELLO_HIP_E_INVALID;
     if (int r = check_target(c, params, out_device, out_stride, true)) return r;
     const auto set_up = [&](Lane &l, bool &new_scene) -> int {
-        new_scene = l.use_own;
-        if (!l.use_own) return 0;
-        // the lane last rendered a vello_hip_render_frame scene: resident frames always show the scene of
+        new_scene = l.which != LaneScene::Shared;
+        if (!new_scene) return 0;
+        // the lane last rendered a scene of its own or the retained list: resident frames always show the scene of
         // vello_hip_upload_scene, whichever lane the rotation has reached
         if (!c->shared.resident) {
             c->last_error = "no scene uploaded (vello_hip_render_frame scenes are private to their frame)";
             return VELLO_HIP_E_INVALID;
         }
         HIP_TRY(c, hipStreamSynchronize(l.stream));
-        l.use_own = false;
+        l.which = LaneScene::Shared;
         return 0;
     };
     int last = VELLO_HIP_STAGE_FINE;
     if (const uint32_t ls = (c->debug_flags >> VELLO_HIP_DEBUG_LAST_STAGE_SHIFT) & 15u) last = (int)ls - 1 < last ? (int)ls - 1 : last;  // (measurement seam)
     return enter_frame(c, params, out_device, out_stride, true, last, set_up, no_step, no_step);
+}
+
+// A frame of the retained instance list under this frame's poses.  Everything that can refuse the frame is asked before the lane
+// is taken; what the host does per frame does not depend on the list's length unless the poses are the host's own.
+int vello_hip_render_retained(vello_hip_ctx *c, const float *transforms, int transforms_is_device, void *src_stream,
+                              const vello_hip_render_params *params, void *out_device, size_t out_stride) {
+    if (!c || !params) return VELLO_HIP_E_INVALID;
+    auto refuse = [&](const std::string &why) {
+        c->last_error = "render_retained: " + why;
+        return VELLO_HIP_E_INVALID;
+    };
+    if (!c->have_retained || !c->retained.resident) return refuse("no retained instance list (vello_hip_retain_instances)");
+    const uint32_t n = c->retained_n;
+    const size_t pose_bytes = (size_t)n * 24u;
+    const bool device = transforms != nullptr && transforms_is_device != 0;
+    if (src_stream && !device) return refuse("src_stream goes with poses in device memory");
+    if (transforms && !device)
+        for (uint32_t i = 0; i < n; i++)
+            for (int k = 0; k < 6; k++) {
+                const float v = transforms[(size_t)i * 6u + k];
+                if (!(v - v == 0.0f)) return refuse("instance " + std::to_string(i) + ": the pose has an entry that is not finite");
+            }
+    if (device) {
+        if ((reinterpret_cast<uintptr_t>(transforms) & 3u) != 0u) return refuse("the address of device poses is not a multiple of 4");
+#ifndef VELLO_SIMT_EMU
+        // every byte the kernel reads lies in one allocation in device memory of this context's device (vello_hip_copy_images_device)
+        if (n != 0u) {
+            hipDeviceptr_t base = nullptr;
+            size_t size = 0;
+            hipPointerAttribute_t attr{};
+            hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<float *>(transforms));
+            if (e == hipSuccess) e = hipPointerGetAttributes(&attr, base);
+            (void)hipGetLastError();  // a host address is an error here: do not leave it for the next launch check
+            if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != c->device)
+                return refuse("the poses are not device memory of device " + std::to_string(c->device));
+            if ((uint64_t)(uintptr_t)transforms + pose_bytes > (uint64_t)(uintptr_t)base + size)
+                return refuse("the poses run past the end of their allocation");
+        }
+#endif
+    }
+    int r;
+    if ((r = check_target(c, params, out_device, out_stride, true))) return r;
+    {
+        Config probe;  // (what prepare_frame would refuse, asked before the lane changes its scene)
+        if ((r = configure(c, c->retained, params, probe))) return r;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (src_stream && !c->pose_mark) HIP_TRY(c, hipEventCreateWithFlags(&c->pose_mark, hipEventDisableTiming));
+    Staging *st = nullptr;
+    const auto set_up = [&](Lane &l, bool &new_scene) -> int {
+        new_scene = l.which != LaneScene::Retained;  // (else: sized when the list was retained, or by the lane's earlier frame of it)
+        if (!new_scene) return 0;
+        HIP_TRY(c, hipStreamSynchronize(l.stream));
+        l.which = LaneScene::Retained;
+        return 0;
+    };
+    const auto staged = [&](Lane &l) -> int {
+        if (transforms && !device) {
+            if (int sr = acquire_staging(c, pose_bytes, st)) return sr;
+            if (int sr = ensure(c, l.poses, pose_bytes)) return sr;
+        }
+        l.pose_src = !transforms ? nullptr : device ? reinterpret_cast<const uint32_t *>(transforms) : (const uint32_t *)l.poses.ptr;
+        l.pose_stream = (hipStream_t)src_stream;
+        l.pose_check = device;
+        return 0;
+    };
+    const auto enqueue = [&](Lane &l) -> int {
+        c->cfg_unsent = true;  // (as an instance frame: VELLO_HIP_BUF_CONFIG gets the Config when it is next read or written)
+        if (st && pose_bytes) {
+            std::memcpy(st->host, transforms, pose_bytes);
+            HIP_TRY(c, hipMemcpyAsync(l.poses.ptr, st->host, pose_bytes, hipMemcpyHostToDevice, l.stream));
+            HIP_TRY(c, hipEventRecord(st->done, l.stream));
+            st->busy = true;
+        }
+        if (src_stream) {  // behind what the caller's stream has been given so far
+            HIP_TRY(c, hipEventRecord(c->pose_mark, (hipStream_t)src_stream));
+            HIP_TRY(c, hipStreamWaitEvent(l.stream, c->pose_mark, 0));
+        }
+        return 0;
+    };
+    Lane &lane = c->lanes[c->next_lane % c->n_active];  // (the lane enter_frame takes)
+    r = enter_frame(c, params, out_device, out_stride, false, VELLO_HIP_STAGE_FINE, set_up, staged, enqueue);
+    // the poses belonged to this frame, enqueued or refused: the lane keeps neither the caller's memory nor the caller's stream
+    lane.pose_src = nullptr;
+    lane.pose_stream = nullptr;
+    lane.pose_check = false;
+    return r;
 }
 
 int vello_hip_run_stages(vello_hip_ctx *c, const vello_hip_render_params *params, int first, int last) {
@@ -456,6 +571,14 @@ int vello_hip_run_stages(vello_hip_ctx *c, const vello_hip_render_params *params
     Frame f;
     int r = prepare_frame(c, l, params, nullptr, 0, f, true);
     if (r) return r;
+    if (f.retained) {
+        // after a retained frame: the lane's copy holds that frame's composed words and the stages go on from them -- its poses may
+        // have been the caller's device memory, which is not read again; a lane that holds none of this list (a list retained
+        // since) gets the rest poses
+        f.pose_stream = nullptr;
+        f.pose_check = false;
+        f.pose_words = l.posed_generation == c->retained.generation ? nullptr : (const uint32_t *)c->retained_rest.ptr;
+    }
     if ((r = run_stage_range(c, l, f, first, last))) return r;
     HIP_TRY(c, hipStreamSynchronize(l.stream));
     return VELLO_HIP_OK;

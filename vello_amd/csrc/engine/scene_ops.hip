@@ -84,6 +84,79 @@ void launch_view_transforms(const Frame &f, hipStream_t s) {
                        const_cast<uint32_t *>(f.scene) + (f.xf_base - 6u));
 }
 
+// a . b as vello_encoding's Transform::mul computes it (math.rs:51-73) -- k_view_transforms' arithmetic: f32, every product and every
+// sum rounded on its own, in this operand order and association
+__device__ __forceinline__ Xform xform_mul(const Xform &a, const Xform &b) {
+    Xform r;
+    r.m0 = a.m0 * b.m0 + a.m2 * b.m1;
+    r.m1 = a.m1 * b.m0 + a.m3 * b.m1;
+    r.m2 = a.m0 * b.m2 + a.m2 * b.m3;
+    r.m3 = a.m1 * b.m2 + a.m3 * b.m3;
+    r.t0 = (a.m0 * b.t0 + a.m2 * b.t1) + a.t0;
+    r.t1 = (a.m1 * b.t0 + a.m3 * b.t1) + a.t1;
+    return r;
+}
+
+// k_instance_transforms: the composed transform words of a frame of the retained instance list (vello_hip_render_retained; the
+// arguments are in engine.h), a lane per transform entry as k_view_transforms -- which it replaces for such a frame.  Slot 0 of `out`
+// is the six words below the retained scene's transform stream, verbatim; slot e + 1 is X.T_e with X the pose of the instance that
+// owns entry e, rounded to six f32 words, and with a view View.(X.T_e): both products in this one kernel, each by xform_mul.
+// A lane reads its owner with its neighbours' (one coalesced dword load a wave), the six words of T at the 24-byte stride
+// k_view_transforms reads them at (a wave's entries are 1.5 KB of consecutive memory) and the six words of its owner's pose: owners do
+// not decrease along the stream, so a wave's poses are the poses of a run of instances -- one or two cache lines where an instance
+// holds several entries, 1.5 KB read like T where every instance holds one.  Dword accesses throughout: stream, poses and copy
+// are 4-byte aligned only.  No LDS: nothing is shared beyond what the cache holds.
+// Where the poses are the caller's device memory (Frame::pose_check) the same grid tests them: lane i < n tests pose i, whether or
+// not instance i owns an entry, and a NaN or an infinity ORs FAILED_SCENE into the frame's bump.failed -- that launch sits behind
+// the frame's zero fill and ahead of its pathtag scan, so the frame is discarded as one whose tag stream contradicts its scene.
+// `failed` is null for host poses and the rest poses, which the host has tested: no test, and the grid covers the entries only.
+__global__ void __launch_bounds__(256) k_instance_transforms(InstanceXfArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (a.failed != nullptr && i < a.n) {
+        const uint32_t *p = a.poses + (size_t)i * 6u;
+        bool finite = true;
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) finite = finite && (p[k] & 0x7f800000u) != 0x7f800000u;
+        if (!finite) atomicOr(a.failed, FAILED_SCENE);
+    }
+    if (i > a.n_xf) return;
+    uint32_t *o = a.out + (size_t)i * 6u;
+    if (i == 0u) {
+        const bool below = a.transform_base >= 6u;
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) o[k] = below ? a.scene[a.transform_base - 6u + k] : 0u;
+        return;
+    }
+    const uint32_t owner = a.owner[i - 1u];  // < n: the host built the table from the list it retained
+    const Xform t = read_transform(a.scene, a.transform_base, i - 1u);
+    const Xform x = read_transform(a.poses, 0u, owner);
+    Xform r = xform_mul(x, t);
+    if (a.has_view) r = xform_mul(a.view, r);
+    o[0] = __float_as_uint(r.m0);
+    o[1] = __float_as_uint(r.m1);
+    o[2] = __float_as_uint(r.m2);
+    o[3] = __float_as_uint(r.m3);
+    o[4] = __float_as_uint(r.t0);
+    o[5] = __float_as_uint(r.t1);
+}
+
+void launch_instance_transforms(const Frame &f, bool check_poses, hipStream_t s) {  // check_poses: Frame::pose_check, behind the zero fill
+    InstanceXfArgs a{};
+    a.scene = f.scene;
+    a.owner = f.xf_owner;
+    a.poses = f.pose_words;
+    a.out = const_cast<uint32_t *>(f.scene) + (f.xf_base - 6u);  // (slot 0 of the copy is entry -1: six words in front of xf_base)
+    a.failed = check_poses ? &f.control->bump.failed : nullptr;
+    a.transform_base = f.cfg.layout.transform_base;
+    a.n_xf = (f.cfg.layout.style_base - f.cfg.layout.transform_base) / 6u;
+    a.n = f.n_instances;
+    a.has_view = f.has_view ? 1u : 0u;
+    a.view = f.view;
+    // (n * 6 and n_xf * 6 are below 2^32: vello_hip_retain_instances)
+    const uint32_t lanes = a.n_xf + 1u > (check_poses ? a.n : 0u) ? a.n_xf + 1u : a.n;
+    hipLaunchKernelGGL(k_instance_transforms, dim3((lanes + 255u) / 256u), dim3(256), 0, s, a);
+}
+
 // k_compose_scene: a frame's packed scene written from instances of the library's fragments (vello_hip_render_instances; the contract is
 // in include/vello_hip.h, the arguments in engine.h).  A thread per destination word, a workgroup per chunk of steps x 256 consecutive
 // words of ONE stream, lane i of a wave on word base + i as in k_atlas_copy.  Which instance a word belongs to is a search for the last

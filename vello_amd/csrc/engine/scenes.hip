@@ -1,4 +1,5 @@
-// Scenes: making a packed scene resident in a slot, the shared scene as a library of fragments, frames composed from instances.
+// Scenes: making a packed scene resident in a slot, the shared scene as a library of fragments, frames composed from instances,
+// an instance list retained across frames.
 #include <cstring>
 
 #include "ctx.h"
@@ -53,7 +54,7 @@ int size_slot(vello_hip_ctx *c, SceneSlot &sc, const vello_hip_layout &L, size_t
     // 64 B of slack: flatten reads tag ix+1 and the (wrapped) style word of pre-style tags speculatively
     // ... and, behind them, room for the composed transform words of frames with a view (SceneSlot::view_at)
     const uint32_t set_words = ((L.style_base - L.transform_base) / 6u + 1u) * 6u;
-    const uint32_t sets = &sc == &c->shared ? MAX_LANES : 1u;
+    const uint32_t sets = &sc == &c->shared || &sc == &c->retained ? MAX_LANES : 1u;
     if ((r = ensure_scene(c, sc, scene_len + 64, (size_t)set_words * sets * 4u))) return r;
     sc.view_sets = sets;
     sc.view_set_words = set_words;
@@ -215,9 +216,72 @@ int plan_instances(vello_hip_ctx *c, const vello_hip_instance *inst, const vello
     return VELLO_HIP_OK;
 }
 
+// The table of an instance list as k_compose_scene reads it (engine.h ComposeArgs): six exclusive prefixes, the fragment indices, the
+// transforms and -- with a paint list -- the paints, written to `table` (compose_table_words(n, paints) words).
+void fill_compose_table(vello_hip_ctx *c, const vello_hip_instance *inst, const vello_hip_paint *paints, uint32_t n, uint32_t *table) {
+    uint32_t *off[6], run[6] = {};
+    for (int s = 0; s < 6; s++) off[s] = table + (size_t)s * (n + 1u);
+    uint32_t *frag_of = table + 6u * ((size_t)n + 1u);
+    for (uint32_t i = 0; i < n; i++) {
+        const FragmentInfo &fi = c->fragments[inst[i].fragment];
+        for (int s = 0; s < 6; s++) {
+            off[s][i] = run[s];
+            run[s] += fi.len[s];
+        }
+        frag_of[i] = inst[i].fragment;
+        std::memcpy(frag_of + n + (size_t)i * 6u, inst[i].transform, 24);
+    }
+    for (int s = 0; s < 6; s++) off[s][n] = run[s];
+    if (paints && n) std::memcpy(frag_of + 7u * (size_t)n, paints, (size_t)n * sizeof *paints);
+}
+
+// k_compose_scene (its painted form with a paint list) of the planned list from the device copy of its table into `dst`, on `st`
+int launch_compose(vello_hip_ctx *c, const ComposePlan &p, uint32_t n, bool painted, const uint32_t *table_dev, uint32_t *dst, hipStream_t st) {
+    ComposeArgs a{};
+    a.lib = (const uint32_t *)c->shared.scene.ptr;
+    a.dst = dst;
+    a.table = table_dev;
+    a.frags = (const uint32_t *)c->frag_table.ptr;
+    a.n = n;
+    const vello_hip_layout &S = c->shared.layout, &D = p.layout;
+    const uint32_t src_base[6] = {S.path_tag_base, S.path_data_base, S.draw_tag_base, S.draw_data_base, S.transform_base, S.style_base};
+    const uint32_t dst_base[6] = {D.path_tag_base, D.path_data_base, D.draw_tag_base, D.draw_data_base, D.transform_base, D.style_base};
+    const uint64_t total = p.scene_len / 4u;
+    uint64_t steps = (total + 256u * COMPOSE_TARGET_WGS - 1u) / (256u * COMPOSE_TARGET_WGS);
+    steps = steps < 1u ? 1u : steps > COMPOSE_MAX_STEPS ? COMPOSE_MAX_STEPS : steps;
+    a.steps = (uint32_t)steps;
+    uint32_t wg = 0u;
+    for (int s = 0; s < 6; s++) {
+        a.src_base[s] = src_base[s];
+        a.dst_base[s] = dst_base[s];
+        a.len[s] = s == 0 ? p.tag_words : p.len[s];
+        a.wg_first[s] = wg;
+        wg += (uint32_t)(((uint64_t)a.len[s] + steps * 256u - 1u) / (steps * 256u));  // (< 2^32 words / 256 in all)
+    }
+    a.wg_first[6] = wg;
+    a.tag_bytes = p.len[0];
+    ComposePaintArgs pa{};
+    if (painted) {
+        pa.paints = a.table + 6u * ((size_t)n + 1u) + 7u * (size_t)n;
+        pa.frag_bits = (const uint32_t *)c->frag_masks.ptr;
+        pa.masks = pa.frag_bits + c->fragments.size();
+    }
+    launch_compose_scene(a, painted ? &pa : nullptr, st);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 namespace vk {
+
+// The retained instance list goes with the fragment table it was composed from (the callers have waited for the frames in flight).
+// Its buffers stay for the next list; vello_hip_release_retained frees them.
+void drop_retained(vello_hip_ctx *c) {
+    c->have_retained = false;
+    c->retained.resident = false;
+    c->retained_n = 0;
+}
 
 // Validates the layout, sizes the slot and copies scene + ramps on `st`; returns once the source buffers may be
 // reused (they are caller-owned only for the duration of the call, recording.rs:124-129).
@@ -276,9 +340,10 @@ int vello_hip_upload_scene(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
     c->have_fragments = false;  // (vello_hip_upload_fragments sets its table once the scene is resident)
     c->have_masks = false;
     c->fragments.clear();
+    drop_retained(c);
     if ((r = load_slot(c, c->shared, c->lanes[0].stream, scene, scene_len, layout, ramps, n_ramps))) return r;
     for (auto &l : c->lanes) {
-        l.use_own = false;
+        l.which = LaneScene::Shared;
         if ((r = alloc_lane_scene(c, l, c->shared))) return r;
     }
     return VELLO_HIP_OK;
@@ -295,6 +360,7 @@ int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t sc
     c->have_fragments = false;
     c->have_masks = false;
     c->fragments.clear();
+    drop_retained(c);
     if (n_frags > 0u && !frags) {
         c->last_error = "upload_fragments: frags is NULL";
         return VELLO_HIP_E_INVALID;
@@ -381,7 +447,7 @@ int vello_hip_render_instances_painted(vello_hip_ctx *c, const vello_hip_instanc
         l.own.brushes = p.brushes;
         l.own.composed = true;
         l.own.n_ramps = 0;
-        l.use_own = true;
+        l.which = LaneScene::Own;
         return 0;
     };
     const auto staged = [&](Lane &l) -> int {
@@ -394,59 +460,12 @@ int vello_hip_render_instances_painted(vello_hip_ctx *c, const vello_hip_instanc
     const auto enqueue = [&](Lane &l) -> int {
         // the Config was not sent (a blocking copy): VELLO_HIP_BUF_CONFIG gets it when it is next read or written
         c->cfg_unsent = true;
-        // the table (engine.h ComposeArgs): six exclusive prefixes, the fragment indices, the transforms
-        uint32_t *table = (uint32_t *)st->host;
-        {
-            uint32_t *off[6], run[6] = {};
-            for (int s = 0; s < 6; s++) off[s] = table + (size_t)s * (n + 1u);
-            uint32_t *frag_of = table + 6u * ((size_t)n + 1u);
-            for (uint32_t i = 0; i < n; i++) {
-                const FragmentInfo &fi = c->fragments[inst[i].fragment];
-                for (int s = 0; s < 6; s++) {
-                    off[s][i] = run[s];
-                    run[s] += fi.len[s];
-                }
-                frag_of[i] = inst[i].fragment;
-                std::memcpy(frag_of + n + (size_t)i * 6u, inst[i].transform, 24);
-            }
-            for (int s = 0; s < 6; s++) off[s][n] = run[s];
-            if (paints && n) std::memcpy(frag_of + 7u * (size_t)n, paints, (size_t)n * sizeof *paints);
-        }
-        ComposeArgs a{};
-        a.lib = (const uint32_t *)c->shared.scene.ptr;
-        a.dst = (uint32_t *)l.own.scene.ptr;
-        a.table = (const uint32_t *)l.compose_table.ptr;
-        a.frags = (const uint32_t *)c->frag_table.ptr;
-        a.n = n;
-        const vello_hip_layout &S = c->shared.layout, &D = p.layout;
-        const uint32_t src_base[6] = {S.path_tag_base, S.path_data_base, S.draw_tag_base, S.draw_data_base, S.transform_base, S.style_base};
-        const uint32_t dst_base[6] = {D.path_tag_base, D.path_data_base, D.draw_tag_base, D.draw_data_base, D.transform_base, D.style_base};
-        const uint64_t total = p.scene_len / 4u;
-        uint64_t steps = (total + 256u * COMPOSE_TARGET_WGS - 1u) / (256u * COMPOSE_TARGET_WGS);
-        steps = steps < 1u ? 1u : steps > COMPOSE_MAX_STEPS ? COMPOSE_MAX_STEPS : steps;
-        a.steps = (uint32_t)steps;
-        uint32_t wg = 0u;
-        for (int s = 0; s < 6; s++) {
-            a.src_base[s] = src_base[s];
-            a.dst_base[s] = dst_base[s];
-            a.len[s] = s == 0 ? p.tag_words : p.len[s];
-            a.wg_first[s] = wg;
-            wg += (uint32_t)(((uint64_t)a.len[s] + steps * 256u - 1u) / (steps * 256u));  // (< 2^32 words / 256 in all)
-        }
-        a.wg_first[6] = wg;
-        a.tag_bytes = p.len[0];
+        fill_compose_table(c, inst, paints, n, (uint32_t *)st->host);
         l.own.resident = false;
         HIP_TRY(c, hipMemcpyAsync(l.compose_table.ptr, st->host, table_bytes, hipMemcpyHostToDevice, l.stream));
         HIP_TRY(c, hipEventRecord(st->done, l.stream));
         st->busy = true;
-        ComposePaintArgs pa{};
-        if (paints) {
-            pa.paints = a.table + 6u * ((size_t)n + 1u) + 7u * (size_t)n;
-            pa.frag_bits = (const uint32_t *)c->frag_masks.ptr;
-            pa.masks = pa.frag_bits + c->fragments.size();
-        }
-        launch_compose_scene(a, paints ? &pa : nullptr, l.stream);
-        HIP_TRY(c, hipGetLastError());
+        if (int lr = launch_compose(c, p, n, paints != nullptr, (const uint32_t *)l.compose_table.ptr, (uint32_t *)l.own.scene.ptr, l.stream)) return lr;
         l.own.resident = true;
         return 0;
     };
@@ -457,6 +476,79 @@ int vello_hip_render_instances_painted(vello_hip_ctx *c, const vello_hip_instanc
 int vello_hip_render_instances(vello_hip_ctx *c, const vello_hip_instance *inst, uint32_t n, const vello_hip_render_params *params, void *out_device,
                                size_t out_stride) {
     return vello_hip_render_instances_painted(c, inst, nullptr, n, params, out_device, out_stride);
+}
+
+// The instance list composed ONCE into the context's retained slot.  Five streams are k_compose_scene's (its painted form with a
+// paint list), as an instance frame's; the transform stream is then written over from the host with the library's entries
+// verbatim -- copied, not multiplied by an identity, which would turn a -0 into +0 -- and, in the same pass over the list, the host
+// builds the table that names each entry's instance and collects the rest poses.  Runs once per list: blocking copies, and it waits
+// for the frames in flight, which may be reading the list it replaces.
+int vello_hip_retain_instances(vello_hip_ctx *c, const vello_hip_instance *inst, const vello_hip_paint *paints, uint32_t n) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    ComposePlan p;
+    int r = plan_instances(c, inst, paints, n, p);
+    if (r) return r;
+    if ((uint64_t)n * 6u > 0xffffffffull) {  // (k_instance_transforms indexes the poses in u32 words)
+        c->last_error = "retain_instances: more than 2^32 / 6 instances";
+        return VELLO_HIP_E_INVALID;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((r = sync_all(c))) return r;
+    // from here on a failure leaves no list retained
+    drop_retained(c);
+    SceneSlot &sc = c->retained;
+    if ((r = size_slot(c, sc, p.layout, p.scene_len))) return r;
+    sc.brushes = p.brushes;
+    sc.composed = true;
+    sc.n_ramps = 0;
+    const uint32_t n_xf = p.len[4] / 6u;
+    // the table, the transform stream as the library holds it, the owners, the rest poses
+    std::vector<uint32_t> table(compose_table_words(n, paints != nullptr));
+    fill_compose_table(c, inst, paints, n, table.data());
+    std::vector<uint32_t> lib_xf(c->shared.layout.style_base - c->shared.layout.transform_base), xf(p.len[4]), owner(n_xf), rest((size_t)n * 6u);
+    if (!lib_xf.empty())
+        HIP_TRY(c, hipMemcpy(lib_xf.data(), (const uint32_t *)c->shared.scene.ptr + c->shared.layout.transform_base, lib_xf.size() * 4u, hipMemcpyDeviceToHost));
+    size_t at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const FragmentInfo &fi = c->fragments[inst[i].fragment];
+        if (fi.len[4]) std::memcpy(&xf[at], &lib_xf[fi.begin[4]], (size_t)fi.len[4] * 4u);
+        for (uint32_t e = 0; e < fi.len[4] / 6u; e++) owner[at / 6u + e] = i;
+        at += fi.len[4];
+        std::memcpy(&rest[(size_t)i * 6u], inst[i].transform, 24);
+    }
+    DevBuf table_dev;  // (freed on the way out: the list is composed once)
+    if ((r = ensure(c, table_dev, table.size() * 4u))) return r;
+    if ((r = ensure(c, c->retained_owner, owner.size() * 4u))) return r;
+    if ((r = ensure(c, c->retained_rest, rest.size() * 4u))) return r;
+    hipStream_t st = c->lanes[0].stream;
+    HIP_TRY(c, hipMemcpy(table_dev.ptr, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
+    if ((r = launch_compose(c, p, n, paints != nullptr, (const uint32_t *)table_dev.ptr, (uint32_t *)sc.scene.ptr, st))) return r;
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (!xf.empty()) HIP_TRY(c, hipMemcpy((uint32_t *)sc.scene.ptr + p.layout.transform_base, xf.data(), xf.size() * 4u, hipMemcpyHostToDevice));
+    if (!owner.empty()) HIP_TRY(c, hipMemcpy(c->retained_owner.ptr, owner.data(), owner.size() * 4u, hipMemcpyHostToDevice));
+    if (!rest.empty()) HIP_TRY(c, hipMemcpy(c->retained_rest.ptr, rest.data(), rest.size() * 4u, hipMemcpyHostToDevice));
+    // the lanes that showed the list this one replaces: their scene-dependent buffers must fit the new one
+    for (auto &l : c->lanes)
+        if (l.which == LaneScene::Retained && (r = alloc_lane_scene(c, l, sc))) return r;
+    c->retained_n = n;
+    sc.resident = true;
+    c->have_retained = true;
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_release_retained(vello_hip_ctx *c) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = sync_all(c)) return r;
+    drop_retained(c);
+    for (DevBuf *b : {&c->retained.scene, &c->retained_owner, &c->retained_rest}) {
+        if (b->ptr) HIP_TRY(c, hipFree(b->ptr));
+        b->ptr = nullptr;
+        b->size = 0;
+    }
+    c->retained.view_cap_bytes = 0;
+    c->retained.view_sets = 0;
+    return VELLO_HIP_OK;
 }
 
 }  // extern "C"

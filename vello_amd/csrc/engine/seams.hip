@@ -146,6 +146,7 @@ int vello_hip_set_debug_flags(vello_hip_ctx *c, uint32_t flags) {
     if (!c) return VELLO_HIP_E_INVALID;
     if ((c->debug_flags ^ flags) & VELLO_HIP_DEBUG_FINE_SLICES) {  // what earlier frames asked for says nothing about the other slice size
         c->shared.slice_demand = -1;
+        c->retained.slice_demand = -1;
         for (auto &l : c->lanes) l.own.slice_demand = -1;
     }
     c->debug_flags = flags;

@@ -335,6 +335,7 @@ class Engine:
         if ramps is not None and len(ramps):
             ramps = np.ascontiguousarray(ramps, dtype=np.uint32)
             rp, nr = ramps.ctypes.data, ramps.size // 512
+        self._retained_n = None  # (an upload drops the retained list)
         self._check(self._lib.vello_hip_upload_scene(self._h, packed.ctypes.data, packed.nbytes, ctypes.byref(lay), rp, nr), "upload_scene")
 
     def resize_image_atlas(self, width, height):
@@ -425,6 +426,7 @@ class Engine:
             for name, _ in FragmentStruct._fields_:
                 b, e = f[name] if isinstance(f, dict) else getattr(f, name)
                 getattr(arr[i], name)[:] = (int(b), int(e))
+        self._retained_n = None  # (an upload drops the retained list)
         self._check(self._lib.vello_hip_upload_fragments(self._h, packed.ctypes.data, packed.nbytes, ctypes.byref(lay), rp, nr, arr,
                                                          len(fragments)), "upload_fragments")
 
@@ -457,6 +459,74 @@ class Engine:
         self._check(self._lib.vello_hip_render_instances_painted(self._h, inst.ctypes.data, pt.ctypes.data, len(inst), ctypes.byref(p), ptr, stride),
                     "render_instances_painted")
 
+    def retain_instances(self, instances, paints=None):
+        """vello_hip_retain_instances: composes `instances` (and `paints`, as render_instances takes them) ONCE into the context's
+        retained scene; render_retained then draws the list under per-frame poses.  Waits for the frames in flight; a second call
+        replaces the list, an upload drops it."""
+        inst = instance_array(instances)
+        pt = None
+        if paints is not None:
+            pt = paint_array(paints)
+            if len(pt) != len(inst):
+                raise ValueError(f"{len(pt)} paints for {len(inst)} instances")
+        self._retained_n = None
+        self._check(self._lib.vello_hip_retain_instances(self._h, inst.ctypes.data, pt.ctypes.data if pt is not None else None, len(inst)),
+                    "retain_instances")
+        self._retained_n = len(inst)
+
+    def render_retained(self, width, height, base_color, aa, transforms=None, out=None, out_stride=None, src_stream=None,
+                        transforms_is_device=False):
+        """vello_hip_render_retained: one frame of the retained list under this frame's poses, enqueued like render_instances.
+        `transforms`: None (the rest poses), an (n, 6) float32 numpy array (host memory: copied during the call), or poses in device
+        memory -- a float32 tensor of n * 6 elements on the engine's GPU, or its address as an int -- which the host never reads.
+        `transforms_is_device` says that a numpy array stands for device memory (the emulated build only).  `src_stream` (a
+        hipStream_t as an int, or a torch stream) is the stream that writes device poses: the frame runs behind it, and it waits for
+        the kernel that reads them."""
+        numpy_is_device = bool(transforms_is_device)
+        p = self._params(width, height, base_color, aa)
+        ptr, stride = None, 0
+        if out is not None:
+            ptr, stride, _ = _target(self._lib, out, width, height, device_only=True, stride=out_stride)
+        n = getattr(self, "_retained_n", None)
+        keep, tp, is_dev = None, None, 0
+        if transforms is None:
+            pass
+        elif isinstance(transforms, np.ndarray):
+            if numpy_is_device and not is_emulated(self._lib):
+                raise ValueError("a numpy array is host memory: device poses are a tensor on the GPU")
+            keep = np.ascontiguousarray(transforms, dtype=np.float32)
+            if n is not None and keep.size != n * 6:
+                raise ValueError(f"{keep.size} floats for {n} retained instances (6 each)")
+            tp, is_dev = keep.ctypes.data, int(numpy_is_device)
+        elif hasattr(transforms, "data_ptr"):
+            import torch
+
+            if transforms.dtype != torch.float32 or not transforms.is_contiguous():
+                raise ValueError("poses are a contiguous float32 tensor of n * 6 elements")
+            if n is not None and transforms.numel() != n * 6:
+                raise ValueError(f"{transforms.numel()} floats for {n} retained instances (6 each)")
+            if transforms.is_cuda:
+                tp, is_dev = transforms.data_ptr(), 1
+            else:
+                keep = transforms.numpy()
+                tp = keep.ctypes.data
+        else:
+            tp, is_dev = int(transforms), 1
+        relay = None
+        if hasattr(src_stream, "cuda_stream"):
+            s, relay = _source_stream(src_stream)
+        else:
+            s = src_stream
+        r = self._lib.vello_hip_render_retained(self._h, tp, is_dev, ctypes.c_void_p(int(s)) if s else None, ctypes.byref(p), ptr, stride)
+        if relay is not None:
+            relay[0].wait_stream(relay[1])
+        self._check(r, "render_retained")
+
+    def release_retained(self):
+        """vello_hip_release_retained: frees the retained list (fine when there is none)."""
+        self._retained_n = None
+        self._check(self._lib.vello_hip_release_retained(self._h), "release_retained")
+
     def render_resident(self, width, height, base_color, aa, out=None, out_stride=None):
         """vello_hip_render_resident.  `out`: a dense uint8 target of height * width * 4 bytes, or an [H, W, 4] view whose rows lie
         stride(0) bytes apart (_target); `out_stride` (bytes) overrides the stride taken from it."""
@@ -486,6 +556,7 @@ class Engine:
         if ramps is not None and len(ramps):
             ramps = np.ascontiguousarray(ramps, dtype=np.uint32)
             rp, nr = ramps.ctypes.data, ramps.size // 512
+        self._retained_n = None  # (its upload drops the retained list)
         r = self._lib.vello_hip_render(self._h, packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p), rp, nr,
                                        out_ptr, stride, 1 if is_dev else 0, ctypes.byref(b))
         if r != 0 and r != E_CAPACITY:
