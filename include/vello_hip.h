@@ -31,6 +31,7 @@
  *   vello_hip_render_retained /   out of the frame loop: the composed scene  vello_encoding/src/encoding.rs:95-152,
  *   vello_hip_release_retained    is kept, a frame brings only the          vello_encoding/src/math.rs:51-73
  *                              transforms of its appends (Transform::mul)
+ *   vello_hip_pick             (none upstream: the reference has no hit test; the contract is stated at the entry point)
  *   vello_hip_sync             queue.submit + device.poll                vello/src/wgpu_engine.rs:757
  *   vello_hip_set_frames_in_flight  back-to-back queue.submit without waiting  vello/src/wgpu_engine.rs:757
  *   vello_hip_get_bump         the robust path's bump download           vello/src/lib.rs:730, :753-761
@@ -466,6 +467,61 @@ int vello_hip_render_retained(vello_hip_ctx *ctx, const float *transforms /* n x
                               size_t out_stride);
 int vello_hip_release_retained(vello_hip_ctx *ctx);
 
+/* Hit testing: the topmost draw object, and the instance that owns it, under each of n points of the frame submitted last on the
+ * context -- the frame whose buffers vello_hip_read_buffer shows.  The reference has no hit test; like instances and views this
+ * extends the boundary, and the contract is stated here.  Everything is read from what the frame left on the device (the line soup,
+ * the draw monoids, the path boxes' draw flags, the composition's draw-tag prefix): no geometry is flattened on the host, a retained
+ * list whose poses live only in device memory is answered like any other frame, and a view transform or poses need no handling of
+ * their own -- the soup is in target space already.
+ *   A point is (qx, qy) in target pixel coordinates: f32, y down, pixel (x, y) centred on (x + 0.5, y + 0.5).
+ *   1. WINDING of a path at the point, over the frame's line soup (lines with path_ix >= n_paths are skipped).  For a line (p0, p1)
+ *      all six f32 values are promoted to f64 and d = (p1x - p0x) * (qy - p0y) - (qx - p0x) * (p1y - p0y) is formed without
+ *      contraction into FMA.  An upward line (p0y <= qy && qy < p1y) adds +1 when d < 0; a downward line (p1y <= qy && qy < p0y)
+ *      adds -1 when d > 0.  Every comparison is written so that a NaN coordinate counts nothing; a point exactly on a line counts
+ *      nothing for that line.  A path is HIT when its winding is != 0 (non-zero fill) or odd (even-odd fill: draw_flags &
+ *      DRAW_INFO_FLAGS_FILL_RULE_BIT of its path box).  The sum does not depend on the order of the lines.  Strokes are in the soup
+ *      as their outlines: a stroke is hit inside its width.
+ *   2. VISIBILITY under clips.  Walking the draw objects in order with a stack: BeginClip pushes the hit bit of its path, a matched
+ *      EndClip pops, a paint draw (fill colour, the three gradients, image, blurred rect) is a CANDIDATE when its own path is hit
+ *      and every bit on the stack is set.  The result is the largest candidate draw index, or VELLO_HIP_PICK_NONE.  Blend modes and
+ *      alpha play no part: a pick is geometric, a transparent fill is still hit.  Clip streams as Scene produces them (balanced) are
+ *      in the contract; for others the result is unspecified, but the call completes.
+ *   3. A point that is not finite, or outside [0, width) x [0, height) of that frame, is VELLO_HIP_PICK_NONE -- which also makes the
+ *      answer independent of vello_hip_set_viewport_cull: the lines culling drops lie above, below or right of the target and
+ *      cannot cross a leftward ray from a point inside it.  Such host points are not refused: a cursor off the window is ordinary
+ *      input.
+ *   4. INSTANCE.  Where the frame was composed from instances (vello_hip_render_instances, _painted, vello_hip_render_retained)
+ *      instance_ix is the instance that owns the draw index: the last entry of the draw-tag stream's prefix that is <= it (empty
+ *      fragments repeat an offset; the last one of a run holds the draw).  For any other frame, and where draw_ix is
+ *      VELLO_HIP_PICK_NONE, it is VELLO_HIP_PICK_NONE.
+ * THE CALL BLOCKS: it waits for the last submitted frame, runs the pick behind it on that frame's stream and returns once `out` is
+ * written -- host memory (out_is_device == 0) or device memory, n entries either way.  `points` is n x 2 floats in host memory
+ * (copied during the call) or in device memory (points_is_device != 0: 4-byte aligned, in one allocation of the context's device);
+ * with `src_stream` (a hipStream_t; device points only) the read of the points waits for what has been enqueued on that stream so
+ * far, as vello_hip_copy_images_device and vello_hip_render_retained order theirs.  n == 0 returns VELLO_HIP_OK and does nothing.
+ * If the frame failed (bump.failed != 0: a pool overflowed and the soup is short, or the scene was bad) the call returns the code
+ * vello_hip_sync reports for it -- VELLO_HIP_E_CAPACITY or VELLO_HIP_E_INVALID -- and writes nothing.  The call changes nothing that
+ * a later vello_hip_sync, vello_hip_get_bump, vello_hip_read_buffer or the next frame sees: it does not move the rotation of the
+ * in-flight buffer sets, allocates no scene buffer and writes none of the frame's buffers (its scratch -- a winding table of
+ * queries x paths words per batch of queries, at most 16 MB unless one query's row is larger -- is the context's own).
+ * VELLO_HIP_E_INVALID, with vello_hip_last_error naming the rule and nothing enqueued: a NULL context, `points` or `out`; n >
+ * VELLO_HIP_PICK_MAX_POINTS; no frame was ever rendered (or its pools were grown or its scene replaced since); src_stream with host
+ * points; a device pointer that is misaligned or (GPU builds) not device memory of the context's device. */
+#define VELLO_HIP_PICK_NONE 0xFFFFFFFFu
+#define VELLO_HIP_PICK_MAX_POINTS 4096u
+typedef struct vello_hip_pick_hit { uint32_t draw_ix, instance_ix; } vello_hip_pick_hit;
+int vello_hip_pick(vello_hip_ctx *ctx, const float *points /* n x 2 */, uint32_t n, int points_is_device,
+                   void *src_stream /* nullable hipStream_t */, vello_hip_pick_hit *out /* n entries */, int out_is_device);
+/* Measurement seam: milliseconds between two events around the launches of the last vello_hip_pick -- every batch's zero fill and two
+ * kernels, not the wait for the frame nor the copies of host points and results -- taken when vello_hip_set_profiling has any stage
+ * enabled; 0 otherwise (scripts/pick_bench.py). */
+int vello_hip_pick_ms(vello_hip_ctx *ctx, float *ms_out);
+/* Test seam: the shapes of the pick's kernels, so that tests place their cases on the boundaries -- lines per workgroup of the line
+ * pass, draw objects per step of the resolve pass, queries per batch under VELLO_HIP_DEBUG_PICK_SMALL_BATCHES, bytes of the
+ * winding-table budget.  0 for any other `which`. */
+enum { VELLO_HIP_PICK_LINES_PER_WORKGROUP = 0, VELLO_HIP_PICK_DRAWS_PER_STEP = 1, VELLO_HIP_PICK_SMALL_BATCH = 2, VELLO_HIP_PICK_SCRATCH_BYTES = 3 };
+uint32_t vello_hip_pick_constant(int which);
+
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a
  * later opaque full-tile cover is normally not emitted; the image is the same, but bump.segments / bump.ptcl and the
  * PTCL words are then <= the reference's): with it set, PTCL, segment slices and every bump counter equal the
@@ -482,9 +538,12 @@ int vello_hip_release_retained(vello_hip_ctx *ctx);
  * the list, and by the scene's size before there is one): same line soup as a multiset -- so that tests can hold both sets of
  * kernels to the oracle on the same scenes.
  * VELLO_HIP_DEBUG_NO_FUSION launches every stage of a small scene as a kernel of its own (normally the workgroups of consecutive
- * stages up to tile_alloc share launches when the scene is small enough for launch boundaries to matter): same buffers. */
+ * stages up to tile_alloc share launches when the scene is small enough for launch boundaries to matter): same buffers.
+ * VELLO_HIP_DEBUG_PICK_SMALL_BATCHES answers the queries of a vello_hip_pick call three at a time (normally as many as fit the
+ * winding-table budget): same answers -- so that a handful of queries on a small scene spans several batches. */
 enum { VELLO_HIP_DEBUG_NO_CULL = 1, VELLO_HIP_DEBUG_STROKE_KERNEL = 2, VELLO_HIP_DEBUG_SEQ_CLIP = 4, VELLO_HIP_DEBUG_FINE_SLICES = 8,
        VELLO_HIP_DEBUG_FLATTEN_COOP = 16, VELLO_HIP_DEBUG_FLATTEN_ALONE = 32, VELLO_HIP_DEBUG_NO_FUSION = 64,
+       VELLO_HIP_DEBUG_PICK_SMALL_BATCHES = 128,
        /* measurement seam: bits 24-27 = 1 + the last stage vello_hip_render_resident launches (0: all of them) -- what the stages
         * up to k cost with frames in flight (scripts/experiments/r6_stage_marginal.py); the frames are incomplete */
        VELLO_HIP_DEBUG_LAST_STAGE_SHIFT = 24 };

@@ -99,6 +99,22 @@ pub struct vello_hip_paint {
     pub rgba: u32,
 }
 
+/// One answer of `vello_hip_pick`: the topmost draw object under the point and the instance that owns it, `VELLO_HIP_PICK_NONE`
+/// where there is none.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vello_hip_pick_hit {
+    pub draw_ix: u32,
+    pub instance_ix: u32,
+}
+
+/// The header's `#define`s of the same names: no draw object / no instance, and the most points of one `vello_hip_pick` call (4096).
+pub const VELLO_HIP_PICK_NONE: u32 = 0xFFFF_FFFF;
+pub const VELLO_HIP_PICK_MAX_POINTS: u32 = 0x1000;
+pub const VELLO_HIP_PICK_LINES_PER_WORKGROUP: c_int = 0;
+pub const VELLO_HIP_PICK_DRAWS_PER_STEP: c_int = 1;
+pub const VELLO_HIP_PICK_SMALL_BATCH: c_int = 2;
+pub const VELLO_HIP_PICK_SCRATCH_BYTES: c_int = 3;
 pub const VELLO_HIP_PAINT_KEEP: u32 = 0;
 pub const VELLO_HIP_PAINT_SOLID: u32 = 1;
 pub const VELLO_HIP_AA_AREA: u32 = 0;
@@ -121,6 +137,7 @@ pub const VELLO_HIP_DEBUG_FINE_SLICES: u32 = 8;
 pub const VELLO_HIP_DEBUG_FLATTEN_COOP: u32 = 16;
 pub const VELLO_HIP_DEBUG_FLATTEN_ALONE: u32 = 32;
 pub const VELLO_HIP_DEBUG_NO_FUSION: u32 = 64;
+pub const VELLO_HIP_DEBUG_PICK_SMALL_BATCHES: u32 = 128;
 pub const VELLO_HIP_STAGE_COUNT: usize = 11;
 
 unsafe extern "C" {
@@ -137,6 +154,9 @@ unsafe extern "C" {
     pub fn vello_hip_retain_instances(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, paints: *const vello_hip_paint, n: u32) -> c_int;
     pub fn vello_hip_render_retained(ctx: *mut vello_hip_ctx, transforms: *const f32, transforms_is_device: c_int, src_stream: *mut c_void, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_release_retained(ctx: *mut vello_hip_ctx) -> c_int;
+    pub fn vello_hip_pick(ctx: *mut vello_hip_ctx, points: *const f32, n: u32, points_is_device: c_int, src_stream: *mut c_void, out: *mut vello_hip_pick_hit, out_is_device: c_int) -> c_int;
+    pub fn vello_hip_pick_ms(ctx: *mut vello_hip_ctx, ms_out: *mut f32) -> c_int;
+    pub fn vello_hip_pick_constant(which: c_int) -> u32;
     pub fn vello_hip_resize_image_atlas(ctx: *mut vello_hip_ctx, width: u32, height: u32) -> c_int;
     pub fn vello_hip_write_image(ctx: *mut vello_hip_ctx, x: u32, y: u32, width: u32, height: u32, rgba8: *const u8, stride: usize) -> c_int;
     pub fn vello_hip_copy_images_device(ctx: *mut vello_hip_ctx, copies: *const vello_hip_image_copy, n: u32, src_stream: *mut c_void) -> c_int;

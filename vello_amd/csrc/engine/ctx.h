@@ -87,6 +87,8 @@ struct Lane {
     DevBuf heavy_list;                // flatten: tag indices for the heavy code, 4 lists (one u32 per tag each, worst case)
     DevBuf arc_items;                 // flatten: arcs the stroke workgroups leave to the heavy code (64 B per segment, worst case)
     DevBuf compose_table;             // vello_hip_render_instances: the frame's ComposeArgs::table (+ ComposePaintArgs::paints)
+    uint32_t compose_n = 0;           // ... and its instance count: vello_hip_pick finds the owner of a draw in the table's draw-tag prefix
+    Config frame_cfg{};               // the Config of the lane's latest frame (prepare_frame): what vello_hip_pick answers against
     // vello_hip_render_retained: the frame's poses when they came from the host (n x 6 words, copied on the lane's stream) ...
     DevBuf poses;
     // ... and where the frame's k_instance_transforms reads them: `poses`, the caller's device memory, or null for the rest poses
@@ -160,9 +162,10 @@ struct vello_hip_ctx {
     // ([n_xf] u32) and the rest poses ([n][6] f32).  Dropped with the fragment table.
     vk::SceneSlot retained;
     vk::DevBuf retained_owner, retained_rest;
+    vk::DevBuf retained_prefix;  // [n + 1] the list's draw-tag prefix (ComposeArgs::table's third row): vello_hip_pick's owner search
     uint32_t retained_n = 0;
     bool have_retained = false;
-    hipEvent_t pose_mark = nullptr;  // orders a retained frame's pose kernel against the caller's src_stream
+    hipEvent_t pose_mark = nullptr;  // orders a retained frame's pose kernel, and vello_hip_pick's read of device points, against the caller's src_stream
     vk::DevBuf atlas;  // persistent image atlas (render.rs:160-176), shared by all lanes
     uint32_t atlas_w = 0, atlas_h = 0;
     std::vector<vk::Lane> lanes;
@@ -182,6 +185,9 @@ struct vello_hip_ctx {
     uint64_t atlas_epoch = 0;  // uploads enqueued so far
     std::vector<vk::Staging> staging;
     vk::DevBuf copy_descs;  // vello_hip_copy_images_device: the batch's AtlasCopyDesc table (written and read on the upload stream only)
+    // vello_hip_pick (blocking: idle between calls): a batch's winding table, host points on their way in, a host result on its way out
+    vk::DevBuf pick_winding, pick_points, pick_out;
+    float pick_ms = 0.f;  // device time of the last pick's launches, taken while profiling is on (vello_hip_pick_ms)
     uint32_t debug_flags = 0;  // VELLO_HIP_DEBUG_*
     bool force_brushes = false;  // pre-warm: run fine's brush specialisation on a scene without brushes
     uint32_t last_render_attempts = 0;  // rounds the last vello_hip_render needed (robust mode)

@@ -324,4 +324,40 @@ inline size_t compose_table_words(uint32_t n, bool painted) { return 6u * ((size
 // pa == nullptr: the unpainted form
 void launch_compose_scene(const ComposeArgs &a, const ComposePaintArgs *pa, hipStream_t s);
 
+// Hit testing (vello_hip_pick, pick.hip): what k_pick_lines and k_pick_resolve are handed by value.  Everything but `winding` and
+// `out` is read only: the frame's line soup, draw monoids and path boxes in its lane, the draw tags of the scene it rendered, and --
+// a frame composed from instances -- the draw-tag stream's exclusive prefix ([n_inst + 1], ComposeArgs::table's third row or the
+// retained list's copy of it).
+//   PICK_LINES_CHUNK  lines per workgroup of k_pick_lines, a lane each;
+//   PICK_DRAW_CHUNK   draw objects per step of k_pick_resolve's walk, a lane each.
+// THE BATCH RULE: the queries of one call are answered in batches of pick_batch(n_paths) queries.  A batch owns a winding table of
+// batch x n_paths u32 words, zero-filled on the frame's stream ahead of its two launches; the table stays within
+// PICK_SCRATCH_BYTES unless ONE query's row is larger (more than 4 Mi paths), which is then a batch of one.
+// VELLO_HIP_DEBUG_PICK_SMALL_BATCHES makes every batch PICK_BATCH_FORCED queries, so that a small scene spans several.
+constexpr uint32_t PICK_LINES_CHUNK = 256u, PICK_DRAW_CHUNK = 256u;
+constexpr uint32_t PICK_NONE = 0xffffffffu, PICK_MAX_POINTS = 4096u;
+constexpr size_t PICK_SCRATCH_BYTES = (size_t)16u << 20;
+constexpr uint32_t PICK_BATCH_FORCED = 3u;
+inline uint32_t pick_batch(uint32_t n_paths, bool forced) {
+    if (forced) return PICK_BATCH_FORCED;
+    if (n_paths == 0u) return PICK_MAX_POINTS;
+    const size_t fit = PICK_SCRATCH_BYTES / ((size_t)n_paths * 4u);
+    return fit < 1u ? 1u : fit > PICK_MAX_POINTS ? PICK_MAX_POINTS : (uint32_t)fit;
+}
+struct PickArgs {
+    const LineSoup *lines;
+    const float *points;            // [n][2] target pixel coordinates, device memory
+    uint32_t *winding;              // [nq][n_paths]
+    const uint32_t *draw_tags;      // [n_draw]
+    const DrawMonoid *draw_monoids;
+    const PathBbox *path_bboxes;
+    const uint32_t *prefix;         // nullable: the frame was not composed from instances
+    uint32_t *out;                  // [n][2] (draw_ix, instance_ix)
+    uint32_t n_lines, n_paths, n_draw, n_inst;
+    uint32_t width, height;         // the frame's target
+    uint32_t q0, nq;                // the batch: queries q0 .. q0 + nq - 1
+};
+void launch_pick_lines(const PickArgs &a, hipStream_t s);    // (nothing to launch for an empty soup or a scene without paths)
+void launch_pick_resolve(const PickArgs &a, hipStream_t s);  // a workgroup per query of the batch
+
 }  // namespace vk

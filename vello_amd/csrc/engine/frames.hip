@@ -286,6 +286,7 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
         f.flatten_coop = coop;
     }
     l.frame_generation = sc.generation;
+    l.frame_cfg = f.cfg;
     f.atlas = c->atlas_w ? (const uint32_t *)c->atlas.ptr : nullptr;
     f.atlas_w = c->atlas_w;
     f.atlas_h = c->atlas_h;

@@ -467,6 +467,7 @@ int vello_hip_render_instances_painted(vello_hip_ctx *c, const vello_hip_instanc
         st->busy = true;
         if (int lr = launch_compose(c, p, n, paints != nullptr, (const uint32_t *)l.compose_table.ptr, (uint32_t *)l.own.scene.ptr, l.stream)) return lr;
         l.own.resident = true;
+        l.compose_n = n;
         return 0;
     };
     // (the rotation moves only once nothing can refuse the frame)
@@ -520,6 +521,7 @@ int vello_hip_retain_instances(vello_hip_ctx *c, const vello_hip_instance *inst,
     if ((r = ensure(c, table_dev, table.size() * 4u))) return r;
     if ((r = ensure(c, c->retained_owner, owner.size() * 4u))) return r;
     if ((r = ensure(c, c->retained_rest, rest.size() * 4u))) return r;
+    if ((r = ensure(c, c->retained_prefix, ((size_t)n + 1u) * 4u))) return r;
     hipStream_t st = c->lanes[0].stream;
     HIP_TRY(c, hipMemcpy(table_dev.ptr, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
     if ((r = launch_compose(c, p, n, paints != nullptr, (const uint32_t *)table_dev.ptr, (uint32_t *)sc.scene.ptr, st))) return r;
@@ -527,6 +529,8 @@ int vello_hip_retain_instances(vello_hip_ctx *c, const vello_hip_instance *inst,
     if (!xf.empty()) HIP_TRY(c, hipMemcpy((uint32_t *)sc.scene.ptr + p.layout.transform_base, xf.data(), xf.size() * 4u, hipMemcpyHostToDevice));
     if (!owner.empty()) HIP_TRY(c, hipMemcpy(c->retained_owner.ptr, owner.data(), owner.size() * 4u, hipMemcpyHostToDevice));
     if (!rest.empty()) HIP_TRY(c, hipMemcpy(c->retained_rest.ptr, rest.data(), rest.size() * 4u, hipMemcpyHostToDevice));
+    // (the table's third row: the exclusive prefix of the instances' draw-tag counts, n + 1 entries)
+    HIP_TRY(c, hipMemcpy(c->retained_prefix.ptr, table.data() + 2u * ((size_t)n + 1u), ((size_t)n + 1u) * 4u, hipMemcpyHostToDevice));
     // the lanes that showed the list this one replaces: their scene-dependent buffers must fit the new one
     for (auto &l : c->lanes)
         if (l.which == LaneScene::Retained && (r = alloc_lane_scene(c, l, sc))) return r;
@@ -541,7 +545,7 @@ int vello_hip_release_retained(vello_hip_ctx *c) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = sync_all(c)) return r;
     drop_retained(c);
-    for (DevBuf *b : {&c->retained.scene, &c->retained_owner, &c->retained_rest}) {
+    for (DevBuf *b : {&c->retained.scene, &c->retained_owner, &c->retained_rest, &c->retained_prefix}) {
         if (b->ptr) HIP_TRY(c, hipFree(b->ptr));
         b->ptr = nullptr;
         b->size = 0;

@@ -28,6 +28,8 @@ BUFFERS = ["scene", "config", "tag_monoids", "path_bboxes", "bump", "lines", "dr
            "output"]
 
 E_CAPACITY = -4
+PICK_NONE = 0xFFFFFFFF  # VELLO_HIP_PICK_NONE: no draw object under the point / the frame was not composed from instances
+PICK_MAX_POINTS = 4096  # VELLO_HIP_PICK_MAX_POINTS
 
 
 class RenderParams:
@@ -320,7 +322,9 @@ class Engine:
 
     def _check(self, r, what):
         if r != 0:
-            raise VelloHipError(f"{what} failed ({r}): {self._lib.vello_hip_last_error(self._h).decode()}")
+            err = VelloHipError(f"{what} failed ({r}): {self._lib.vello_hip_last_error(self._h).decode()}")
+            err.code = r  # the VELLO_HIP_E_* code
+            raise err
 
     @staticmethod
     def _params(width, height, base_color, aa):
@@ -527,6 +531,71 @@ class Engine:
         self._retained_n = None
         self._check(self._lib.vello_hip_release_retained(self._h), "release_retained")
 
+    def pick(self, points, out=None, src_stream=None, points_is_device=None):
+        """vello_hip_pick: the topmost draw object and its instance under each point of the frame submitted last (the contract is in
+        include/vello_hip.h).  `points`: an (n, 2) float32 numpy array (host memory), or a float32 tensor of n * 2 elements -- on the
+        GPU it is read in place, behind `src_stream` (a hipStream_t as an int, or a torch stream) when one is given.
+        `points_is_device` says that a numpy array stands for device memory (the emulated build only).  Returns an (n, 2) uint32 numpy
+        array of (draw_ix, instance_ix), PICK_NONE where there is none; with `out` -- an (n, 2) uint32 numpy array, or an int32 /
+        uint32 tensor of n * 2 elements on the GPU -- the answers are written there and `out` is returned.  Blocks until they are.
+        A frame that failed raises VelloHipError with the code vello_hip_sync reports for it in `.code`."""
+        numpy_is_device = bool(points_is_device)
+        keep, is_dev = None, 0
+        if isinstance(points, np.ndarray):
+            if numpy_is_device and not is_emulated(self._lib):
+                raise ValueError("a numpy array is host memory: device points are a tensor on the GPU")
+            keep = np.ascontiguousarray(points, dtype=np.float32)
+            pp, n2, is_dev = keep.ctypes.data, keep.size, int(numpy_is_device)
+        elif hasattr(points, "data_ptr"):
+            import torch
+
+            if points.dtype != torch.float32 or not points.is_contiguous():
+                raise ValueError("points are a contiguous float32 tensor of n * 2 elements")
+            n2 = points.numel()
+            if points.is_cuda:
+                pp, is_dev = points.data_ptr(), 1
+            else:
+                keep = points.numpy()
+                pp = keep.ctypes.data
+        else:
+            raise ValueError("points are an (n, 2) float32 numpy array or a float32 tensor")
+        if n2 % 2:
+            raise ValueError(f"{n2} floats: points are (x, y) pairs")
+        n = n2 // 2
+        out_dev = 0
+        if out is None:
+            out = np.zeros((n, 2), dtype=np.uint32)
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.uint32 or not out.flags["C_CONTIGUOUS"] or out.size != n2:
+                raise ValueError(f"out must be a C-contiguous uint32 array of {n} x 2 entries")
+            op = out.ctypes.data
+        else:
+            if str(out.dtype) not in ("torch.int32", "torch.uint32") or not out.is_contiguous() or out.numel() != n2 or not out.is_cuda:
+                raise ValueError(f"out must be a contiguous int32 / uint32 tensor of {n} x 2 entries on the GPU (or a numpy array)")
+            op, out_dev = out.data_ptr(), 1
+        relay = None
+        if hasattr(src_stream, "cuda_stream"):
+            s, relay = _source_stream(src_stream)
+        else:
+            s = src_stream
+        r = self._lib.vello_hip_pick(self._h, pp, n, is_dev, ctypes.c_void_p(int(s)) if s else None, op, out_dev)
+        if relay is not None:
+            relay[0].wait_stream(relay[1])
+        self._check(r, "pick")
+        return out
+
+    def pick_ms(self):
+        """vello_hip_pick_ms: device milliseconds of the last pick's launches, taken while set_profiling has any stage enabled."""
+        ms = ctypes.c_float()
+        self._check(self._lib.vello_hip_pick_ms(self._h, ctypes.byref(ms)), "pick_ms")
+        return float(ms.value)
+
+    def pick_constants(self):
+        """vello_hip_pick_constant: the shapes of the pick's kernels (a test seam) -- lines per workgroup of the line pass, draw objects
+        per step of the resolve pass, queries per batch under the pick_small_batches debug flag, bytes of the winding-table budget."""
+        names = ("lines_per_workgroup", "draws_per_step", "small_batch", "scratch_bytes")
+        return {k: int(self._lib.vello_hip_pick_constant(i)) for i, k in enumerate(names)}
+
     def render_resident(self, width, height, base_color, aa, out=None, out_stride=None):
         """vello_hip_render_resident.  `out`: a dense uint8 target of height * width * 4 bytes, or an [H, W, 4] view whose rows lie
         stride(0) bytes apart (_target); `out_stride` (bytes) overrides the stride taken from it."""
@@ -588,20 +657,21 @@ class Engine:
         frames already enqueued keep the view they were enqueued with."""
         self._check(self._lib.vello_hip_set_view_transform(self._h, _view_floats(view)), "set_view_transform")
 
-    def set_debug_flags(self, no_cull=False, stroke_kernel=False, seq_clip=False, fine_slices=False, flatten_coop=False, flatten_alone=False, no_fusion=False):
+    def set_debug_flags(self, no_cull=False, stroke_kernel=False, seq_clip=False, fine_slices=False, flatten_coop=False, flatten_alone=False, no_fusion=False,
+                        pick_small_batches=False):
         """vello_hip_set_debug_flags: no_cull makes coarse emit every draw (reference-exact PTCL / segments); stroke_kernel
         runs flatten's stroked-line kernel whatever the number of stroked lines; seq_clip matches clips with the one-wave
         stack machine instead of the partitioned kernels; fine_slices cuts every tile's command list into slices of
         4 fills for fine's MSAA modes (normally only lists of >= 96 fills are cut, engine.h FINE_SLICE_MIN_FILLS); flatten_coop /
         flatten_alone pick the kernels of flatten's heavy list (the wave-cooperative walk / every lane on its own) instead of leaving
         the choice to the engine; no_fusion launches every stage of a small scene as a kernel of its own (normally consecutive stages
-        up to tile_alloc share launches there).  Flags not named are cleared (update_debug_flags keeps them)."""
+        up to tile_alloc share launches there); pick_small_batches answers a pick's queries three at a time.  Flags not named are cleared (update_debug_flags keeps them)."""
         self._debug = {"no_cull": bool(no_cull), "stroke_kernel": bool(stroke_kernel), "seq_clip": bool(seq_clip),
                        "fine_slices": bool(fine_slices), "flatten_coop": bool(flatten_coop), "flatten_alone": bool(flatten_alone),
-                       "no_fusion": bool(no_fusion)}
+                       "no_fusion": bool(no_fusion), "pick_small_batches": bool(pick_small_batches)}
         d = self._debug
         flags = ((1 if d["no_cull"] else 0) | (2 if d["stroke_kernel"] else 0) | (4 if d["seq_clip"] else 0) | (8 if d["fine_slices"] else 0) |
-                 (16 if d["flatten_coop"] else 0) | (32 if d["flatten_alone"] else 0) | (64 if d["no_fusion"] else 0))
+                 (16 if d["flatten_coop"] else 0) | (32 if d["flatten_alone"] else 0) | (64 if d["no_fusion"] else 0) | (128 if d["pick_small_batches"] else 0))
         self._check(self._lib.vello_hip_set_debug_flags(self._h, flags), "set_debug_flags")
 
     def update_debug_flags(self, **changes):
