@@ -521,6 +521,20 @@ int vello_hip_pick_ms(vello_hip_ctx *ctx, float *ms_out);
  * winding-table budget.  0 for any other `which`. */
 enum { VELLO_HIP_PICK_LINES_PER_WORKGROUP = 0, VELLO_HIP_PICK_DRAWS_PER_STEP = 1, VELLO_HIP_PICK_SMALL_BATCH = 2, VELLO_HIP_PICK_SCRATCH_BYTES = 3 };
 uint32_t vello_hip_pick_constant(int which);
+/* Test seam: the sizes at which the pipeline's kernels and the host's launch switches cut their work, so that tests place tags, draw
+ * objects, clips, lines and tile rows on those boundaries -- tags per partition of the pathtag scan's look-back and per block of
+ * flatten's light pass; draw objects per partition of the draw scan; clips per partition of the clip kernels; draw objects (paths)
+ * per workgroup of binning, tile_alloc and coarse's prepass; draw objects per batch of k_coarse and the number of bins its grid is
+ * rounded up to; lines per chunk of path_count's three forms (soup size unknown with one frame in flight, soup known to be small,
+ * frames in flight); SegmentCounts per workgroup of path_tiling; tiles per block of backdrop's row scan; the most tags and draw
+ * objects (paths) of a scene whose front stages share launches, and the most segments of one whose front is ONE launch.  0 for any
+ * other `which`. */
+enum { VELLO_HIP_SHAPE_PATHTAG_PART_TAGS = 0, VELLO_HIP_SHAPE_FLATTEN_BLOCK_TAGS = 1, VELLO_HIP_SHAPE_DRAW_PART = 2, VELLO_HIP_SHAPE_CLIP_PART = 3,
+       VELLO_HIP_SHAPE_DRAW_WORKGROUP = 4, VELLO_HIP_SHAPE_COARSE_BATCH = 5, VELLO_HIP_SHAPE_COARSE_GRID_BINS = 6,
+       VELLO_HIP_SHAPE_PATH_COUNT_CHUNK = 7, VELLO_HIP_SHAPE_PATH_COUNT_CHUNK_SMALL = 8, VELLO_HIP_SHAPE_PATH_COUNT_CHUNK_IN_FLIGHT = 9,
+       VELLO_HIP_SHAPE_PATH_TILING_WORKGROUP = 10, VELLO_HIP_SHAPE_BACKDROP_BLOCK_TILES = 11, VELLO_HIP_SHAPE_FRONT_MAX_TAGS = 12,
+       VELLO_HIP_SHAPE_FRONT_MAX_DRAW_OBJECTS = 13, VELLO_HIP_SHAPE_FRONT_TINY_SEGMENTS = 14, VELLO_HIP_SHAPE_COUNT = 15 };
+uint32_t vello_hip_stage_constant(int which);
 
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a
  * later opaque full-tile cover is normally not emitted; the image is the same, but bump.segments / bump.ptcl and the

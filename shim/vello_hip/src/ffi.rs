@@ -157,6 +157,7 @@ unsafe extern "C" {
     pub fn vello_hip_pick(ctx: *mut vello_hip_ctx, points: *const f32, n: u32, points_is_device: c_int, src_stream: *mut c_void, out: *mut vello_hip_pick_hit, out_is_device: c_int) -> c_int;
     pub fn vello_hip_pick_ms(ctx: *mut vello_hip_ctx, ms_out: *mut f32) -> c_int;
     pub fn vello_hip_pick_constant(which: c_int) -> u32;
+    pub fn vello_hip_stage_constant(which: c_int) -> u32;
     pub fn vello_hip_resize_image_atlas(ctx: *mut vello_hip_ctx, width: u32, height: u32) -> c_int;
     pub fn vello_hip_write_image(ctx: *mut vello_hip_ctx, x: u32, y: u32, width: u32, height: u32, rgba8: *const u8, stride: usize) -> c_int;
     pub fn vello_hip_copy_images_device(ctx: *mut vello_hip_ctx, copies: *const vello_hip_image_copy, n: u32, src_stream: *mut c_void) -> c_int;

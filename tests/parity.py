@@ -365,9 +365,24 @@ def compare_clip_stage(engine, ops, rng, name, oracle=None):
     return layout
 
 
-def clip_structures(big):
+def clip_partition_structures(part):
+    """(name, ops, edge) for compare_clip_stage, exactly around the clip kernels' partition of `part` clips (Engine.stage_constants()
+    ["clip_part"]; a BeginClip and an EndClip are a clip each).  edge: the index of a push that is the last clip of a partition and
+    whose pop is the first clip of the next (None where the case has none)."""
+    for k in (part - 1, part, part + 1):  # the innermost pair lies below, on and above the partition's edge
+        yield f"nest {k}", [1] * k + [-1] * k, (k - 1 if k == part else None)
+    # a flat run of pairs, shifted by one clip: every partition's edge lies between a push and its pop
+    yield "flat across", [1] + [1, -1] * (part + part // 2) + [-1], part - 1
+    yield "flat 2 partitions", [1, -1] * part, None  # 2 * part clips exactly: the pairs end with the partitions
+
+
+def clip_structures(big, part=None):
     """(name, ops) pairs for compare_clip_stage: +1 pushes a clip layer, -1 pops.  The partitioned kernels cut the clip stream every
-    256 clips: runs, teeth and depths are chosen around that, the stack grows far beyond the 256 entries clip_leaf.wgsl:87-112 holds."""
+    256 clips: runs, teeth and depths are chosen around that, the stack grows far beyond the 256 entries clip_leaf.wgsl:87-112 holds.
+    part: the partition size read from the engine -- the exact cases of clip_partition_structures come first."""
+    if part is not None:
+        for name, ops, _ in clip_partition_structures(part):
+            yield name, ops
     yield "one", [1, -1]
     yield "flat", [1, -1] * 300
     yield "deep", [1] * 700 + [-1] * 700

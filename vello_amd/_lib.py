@@ -113,6 +113,7 @@ def load_library():
     sig("vello_hip_release_retained", i32, [vp])
     sig("vello_hip_pick", i32, [vp, vp, u32, i32, vp, vp, i32])
     sig("vello_hip_pick_constant", u32, [i32])
+    sig("vello_hip_stage_constant", u32, [i32])
     sig("vello_hip_pick_ms", i32, [vp, c.POINTER(c.c_float)])
     sig("vello_hip_set_frames_in_flight", i32, [vp, u32])
     sig("vello_hip_resize_image_atlas", i32, [vp, u32, u32])

@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(256) k_binning_tile_alloc(Config cfg, const Dr
 }
 
 void launch_binning_tile_alloc(const Frame &f, hipStream_t s) {
-    const uint32_t n_b = (f.cfg.layout.n_draw_objects + 255u) / 256u, n_t = (f.cfg.layout.n_paths + 255u) / 256u;
+    const uint32_t n_b = (f.cfg.layout.n_draw_objects + DRAW_WG - 1u) / DRAW_WG, n_t = (f.cfg.layout.n_paths + DRAW_WG - 1u) / DRAW_WG;
     const uint32_t n_wg = n_b > n_t ? n_b : n_t;
     if (n_wg == 0) return;
     hipLaunchKernelGGL(k_binning_tile_alloc, dim3(n_wg), dim3(256), 0, s, f.cfg, f.draw_monoids, f.path_bboxes, f.clip_bboxes, f.draw_bboxes,
@@ -49,14 +49,14 @@ void launch_binning_tile_alloc(const Frame &f, hipStream_t s) {
 }
 
 void launch_binning(const Frame &f, hipStream_t s) {
-    uint32_t n_wg = (f.cfg.layout.n_draw_objects + 255u) / 256u;
+    uint32_t n_wg = (f.cfg.layout.n_draw_objects + DRAW_WG - 1u) / DRAW_WG;
     if (n_wg == 0) return;
     hipLaunchKernelGGL(k_binning, dim3(n_wg), dim3(256), 0, s, f.cfg, f.draw_monoids, f.path_bboxes, f.clip_bboxes, f.draw_bboxes,
                        f.bump(), f.info_bin_data, f.bin_headers);
 }
 
 void launch_tile_alloc(const Frame &f, hipStream_t s) {
-    uint32_t n_wg = (f.cfg.layout.n_paths + 255u) / 256u;
+    uint32_t n_wg = (f.cfg.layout.n_paths + DRAW_WG - 1u) / DRAW_WG;
     if (n_wg == 0) return;
     hipLaunchKernelGGL(k_tile_alloc, dim3(n_wg), dim3(256), 0, s, f.cfg, f.scene, f.draw_bboxes, f.bump(), f.paths, f.tiles);
 }

@@ -806,13 +806,17 @@ int enable_coarse_lds() {
 #endif
 }
 
+constexpr uint32_t COARSE_GRID_BINS = 8u;  // k_coarse's grid is rounded up to this many bins (four workgroups each)
+uint32_t coarse_batch_draws() { return NB; }
+uint32_t coarse_grid_bins() { return COARSE_GRID_BINS; }
+
 void launch_coarse(const Frame &f, hipStream_t s, hipEvent_t *mid) {
     const uint32_t wb = (f.cfg.width_in_tiles + 15u) / 16u, hb = (f.cfg.height_in_tiles + 15u) / 16u;
     if (wb * hb == 0) {
         if (mid) (void)hipEventRecord(mid[0], s);  // (recorded on every way out: vello_hip_get_kernel_ms reads it)
         return;
     }
-    const uint32_t n_el_blocks = (f.cfg.layout.n_draw_objects + 255u) / 256u;
+    const uint32_t n_el_blocks = (f.cfg.layout.n_draw_objects + DRAW_WG - 1u) / DRAW_WG;
     // bit planes: 4 waves x 64 tiles per block and step; sized for the pool (blocks beyond bump.tile exit at once)
     uint32_t n_bit_blocks = (uint32_t)(((uint64_t)f.cfg.tiles_size + 256u * 8u - 1u) / (256u * 8u));
     if (n_bit_blocks > 2048u) n_bit_blocks = 2048u;
@@ -820,7 +824,7 @@ void launch_coarse(const Frame &f, hipStream_t s, hipEvent_t *mid) {
     hipLaunchKernelGGL(k_coarse_prep, dim3(n_el_blocks + n_bit_blocks), dim3(256), 0, s, f.cfg, n_el_blocks, f.scene, f.draw_monoids,
                        f.info_bin_data, f.paths, f.tiles, f.bump(), f.coarse_el, f.tile_bits);
     if (mid) (void)hipEventRecord(mid[0], s);
-    const uint32_t n_wg = ((wb * hb + 7u) / 8u) * 8u * 4u;
+    const uint32_t n_wg = ((wb * hb + COARSE_GRID_BINS - 1u) / COARSE_GRID_BINS) * COARSE_GRID_BINS * 4u;
     hipLaunchKernelGGL(k_coarse, dim3(n_wg), dim3(WG), sizeof(CoarseLds), s, f.cfg, f.scene, f.bin_headers, f.info_bin_data, f.coarse_el, f.tile_bits,
                        f.tiles, f.bump(), f.ptcl, !f.no_cull, f.control->work_count, f.tile_order,
                        f.slice_items, f.slice_counters, f.slice_cap, f.cov_cap, f.slice_fills, f.slice_min_fills);

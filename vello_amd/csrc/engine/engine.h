@@ -13,6 +13,7 @@ namespace vk {
 constexpr uint32_t SCAN_STATUS_AGG = 1, SCAN_STATUS_PREFIX = 2;
 constexpr uint32_t PATHTAG_PART_WORDS = 1024;  // 256 threads x 4 tag words (= 4096 tags)
 constexpr uint32_t DRAW_PART = 256;            // draw objects per partition
+constexpr uint32_t DRAW_WG = 256;              // draw objects (k_binning, k_coarse_prep) or paths (k_tile_alloc) per workgroup: a thread each
 #ifndef VK_FLATTEN_TPT
 #define VK_FLATTEN_TPT 4
 #endif
@@ -273,6 +274,12 @@ void launch_coarse(const Frame &f, hipStream_t s, hipEvent_t *mid = nullptr);
 int enable_coarse_lds();  // hipError_t of the per-device dynamic-LDS opt-in
 void launch_path_tiling(const Frame &f, hipStream_t s);
 void launch_fine(const Frame &f, hipStream_t s);
+// Test seam (vello_hip_stage_constant, seams.hip): the sizes that are named beside the kernels they belong to
+uint32_t coarse_batch_draws();          // coarse.hip NB: draw objects per batch of a bin's list
+uint32_t coarse_grid_bins();            // coarse.hip: k_coarse's grid holds a multiple of this many bins
+uint32_t path_count_chunk(int form);    // path.hip: lines per chunk -- 0: soup size unknown, one frame in flight; 1: small soup; 2: frames in flight
+uint32_t path_tiling_workgroup();       // path.hip: SegmentCounts per workgroup and turn
+uint32_t backdrop_block_tiles();        // path.hip BACKDROP_BLOCK_TILES
 
 // Device-to-atlas copies (vello_hip_copy_images_device, atlas.hip; k_atlas_copy, scene_ops.hip): one rectangle of raw RGBA8 words per entry.  `first` is
 // the exclusive prefix of width * height over the batch, so the batch is one concatenated texel space that k_atlas_copy

@@ -180,7 +180,7 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
     // size-dependent buffers
     uint32_t wb = (f.cfg.width_in_tiles + 15u) / 16u, hb = (f.cfg.height_in_tiles + 15u) / 16u;
     uint32_t aligned_n_bins = align_up(wb * hb, 256u);
-    uint32_t binning_wgs = (sc.layout.n_draw_objects + 255u) / 256u;
+    uint32_t binning_wgs = (sc.layout.n_draw_objects + DRAW_WG - 1u) / DRAW_WG;
     if ((r = ensure(c, l.buf[VELLO_HIP_BUF_BIN_HEADERS], (size_t)(binning_wgs * aligned_n_bins + 1u) * sizeof(BinHeader)))) return r;
     if (!out_device && (r = ensure(c, l.buf[VELLO_HIP_BUF_OUTPUT], (size_t)p->width * p->height * 4u))) return r;
     if ((r = ensure(c, l.tile_order, (size_t)f.cfg.width_in_tiles * f.cfg.height_in_tiles * FINE_WORK_BUCKETS * 4u))) return r;

@@ -822,15 +822,21 @@ static uint32_t clamp_grid(uint64_t work_items, uint32_t per_block, uint32_t max
     return (uint32_t)g;
 }
 
+// lines per chunk of k_path_count's forms (256 threads x the form's lines per thread) and SegmentCounts per workgroup of k_path_tiling
+constexpr uint32_t PATH_COUNT_CHUNK_SMALL = 256u, PATH_COUNT_CHUNK_IN_FLIGHT = 256u * VK_PC_LPT_IN_FLIGHT, PATH_TILING_WG = 256u;
+uint32_t path_count_chunk(int form) { return form == 0 ? PATH_COUNT_CHUNK : form == 1 ? PATH_COUNT_CHUNK_SMALL : form == 2 ? PATH_COUNT_CHUNK_IN_FLIGHT : 0u; }
+uint32_t path_tiling_workgroup() { return PATH_TILING_WG; }
+uint32_t backdrop_block_tiles() { return BACKDROP_BLOCK_TILES; }
+
 void launch_path_count(const Frame &f, hipStream_t s) {
     if (f.path_count_small) {
-        const uint32_t grid = clamp_grid(f.cfg.lines_size, 256u, VK_PC_GRID);
+        const uint32_t grid = clamp_grid(f.cfg.lines_size, PATH_COUNT_CHUNK_SMALL, VK_PC_GRID);
         hipLaunchKernelGGL((k_path_count<1u, PcAlone>), dim3(grid), dim3(256), 0, s, f.cfg, f.bump(), f.lines, f.paths, f.tiles, f.seg_counts);
     } else if (f.flatten_side_by_side) {  // (one frame in flight)
         const uint32_t grid = clamp_grid(f.cfg.lines_size, PATH_COUNT_CHUNK, VK_PC_GRID);
         hipLaunchKernelGGL((k_path_count<PATH_COUNT_LINES_PER_THREAD, PcAlone>), dim3(grid), dim3(256), 0, s, f.cfg, f.bump(), f.lines, f.paths, f.tiles, f.seg_counts);
     } else {  // frames in flight: the small footprint (PcInFlight, above)
-        const uint32_t grid = clamp_grid(f.cfg.lines_size, 256u * VK_PC_LPT_IN_FLIGHT, VK_PC_GRID_IN_FLIGHT);
+        const uint32_t grid = clamp_grid(f.cfg.lines_size, PATH_COUNT_CHUNK_IN_FLIGHT, VK_PC_GRID_IN_FLIGHT);
         hipLaunchKernelGGL((k_path_count<VK_PC_LPT_IN_FLIGHT, PcInFlight>), dim3(grid), dim3(256), 0, s, f.cfg, f.bump(), f.lines, f.paths, f.tiles, f.seg_counts);
     }
 }
@@ -851,7 +857,7 @@ void launch_path_tiling(const Frame &f, hipStream_t s) {
 #ifndef VK_PT_GRID_IN_FLIGHT
 #define VK_PT_GRID_IN_FLIGHT 2048u  // (sweep constant: the grid's cap with frames in flight)
 #endif
-    uint32_t grid = clamp_grid(f.cfg.seg_counts_size, 256u, f.flatten_side_by_side ? 2048u : VK_PT_GRID_IN_FLIGHT);
+    uint32_t grid = clamp_grid(f.cfg.seg_counts_size, PATH_TILING_WG, f.flatten_side_by_side ? 2048u : VK_PT_GRID_IN_FLIGHT);
     hipLaunchKernelGGL(k_path_tiling, dim3(grid), dim3(256), 0, s, f.cfg, f.bump(), f.seg_counts, f.lines, f.paths, f.tiles,
                        f.segments, f.ptcl);
 }

@@ -131,6 +131,27 @@ const char *vello_hip_stage_name(int stage) {
     return kStageNames[stage];
 }
 
+uint32_t vello_hip_stage_constant(int which) {
+    switch (which) {
+    case VELLO_HIP_SHAPE_PATHTAG_PART_TAGS: return PATHTAG_PART_WORDS * 4u;
+    case VELLO_HIP_SHAPE_FLATTEN_BLOCK_TAGS: return FLATTEN_BLOCK_TAGS;
+    case VELLO_HIP_SHAPE_DRAW_PART: return DRAW_PART;
+    case VELLO_HIP_SHAPE_CLIP_PART: return CLIP_PART;
+    case VELLO_HIP_SHAPE_DRAW_WORKGROUP: return DRAW_WG;
+    case VELLO_HIP_SHAPE_COARSE_BATCH: return coarse_batch_draws();
+    case VELLO_HIP_SHAPE_COARSE_GRID_BINS: return coarse_grid_bins();
+    case VELLO_HIP_SHAPE_PATH_COUNT_CHUNK: return path_count_chunk(0);
+    case VELLO_HIP_SHAPE_PATH_COUNT_CHUNK_SMALL: return path_count_chunk(1);
+    case VELLO_HIP_SHAPE_PATH_COUNT_CHUNK_IN_FLIGHT: return path_count_chunk(2);
+    case VELLO_HIP_SHAPE_PATH_TILING_WORKGROUP: return path_tiling_workgroup();
+    case VELLO_HIP_SHAPE_BACKDROP_BLOCK_TILES: return backdrop_block_tiles();
+    case VELLO_HIP_SHAPE_FRONT_MAX_TAGS: return FRONT_MAX_TAGS;
+    case VELLO_HIP_SHAPE_FRONT_MAX_DRAW_OBJECTS: return FRONT_MAX_DRAW_OBJECTS;
+    case VELLO_HIP_SHAPE_FRONT_TINY_SEGMENTS: return FRONT_TINY_SEGMENTS;
+    default: return 0u;
+    }
+}
+
 size_t vello_hip_buffer_size(vello_hip_ctx *c, int id) {
     if (!c || id < 0 || id >= VELLO_HIP_BUF_COUNT) return 0;
     return find_buf(c, id).size;

@@ -596,6 +596,15 @@ class Engine:
         names = ("lines_per_workgroup", "draws_per_step", "small_batch", "scratch_bytes")
         return {k: int(self._lib.vello_hip_pick_constant(i)) for i, k in enumerate(names)}
 
+    STAGE_CONSTANTS = ("pathtag_part_tags", "flatten_block_tags", "draw_part", "clip_part", "draw_workgroup", "coarse_batch", "coarse_grid_bins",
+                       "path_count_chunk", "path_count_chunk_small", "path_count_chunk_in_flight", "path_tiling_workgroup", "backdrop_block_tiles",
+                       "front_max_tags", "front_max_draw_objects", "front_tiny_segments")
+
+    def stage_constants(self):
+        """vello_hip_stage_constant: the sizes at which the pipeline's kernels and the host's launch switches cut their work (a test
+        seam; include/vello_hip.h lists them), by name."""
+        return {k: int(self._lib.vello_hip_stage_constant(i)) for i, k in enumerate(self.STAGE_CONSTANTS)}
+
     def render_resident(self, width, height, base_color, aa, out=None, out_stride=None):
         """vello_hip_render_resident.  `out`: a dense uint8 target of height * width * 4 bytes, or an [H, W, 4] view whose rows lie
         stride(0) bytes apart (_target); `out_stride` (bytes) overrides the stride taken from it."""
