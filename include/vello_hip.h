@@ -31,6 +31,8 @@
  *   vello_hip_render_retained /   out of the frame loop: the composed scene  vello_encoding/src/encoding.rs:95-152,
  *   vello_hip_release_retained    is kept, a frame brings only the          vello_encoding/src/math.rs:51-73
  *                              transforms of its appends (Transform::mul)
+ *   vello_hip_render_retained_painted  ... and this frame's solid brushes  vello_encoding/src/encoding.rs:280-290
+ *                              (encode_brush per appended scene)
  *   vello_hip_pick             (none upstream: the reference has no hit test; the contract is stated at the entry point)
  *   vello_hip_sync             queue.submit + device.poll                vello/src/wgpu_engine.rs:757
  *   vello_hip_set_frames_in_flight  back-to-back queue.submit without waiting  vello/src/wgpu_engine.rs:757
@@ -458,13 +460,57 @@ int vello_hip_render_instances_painted(vello_hip_ctx *ctx, const vello_hip_insta
  *      vello_hip_render_instances: VELLO_HIP_E_CAPACITY at vello_hip_sync, then vello_hip_grow_pools and a second call.  A
  *      refused frame (VELLO_HIP_E_INVALID: no retained list, a pose or a pose source as rule 3 refuses it, a target or render
  *      parameters that are refused) enqueues nothing and leaves the rotation where it was.
- *   5. Out of scope: per-frame paints (colour words sit in draw data, which has no per-frame copy: retain again); per-frame
- *      changes of membership or order (retain again); pool estimation for instance lists; more than one retained list per
- *      context. */
+ *   5. Out of scope: per-frame changes of membership or order (retain again); pool estimation for instance lists; more than one
+ *      retained list per context.  Per-frame paints are vello_hip_render_retained_painted, below. */
 int vello_hip_retain_instances(vello_hip_ctx *ctx, const vello_hip_instance *inst, const vello_hip_paint *paints /* nullable */, uint32_t n);
 int vello_hip_render_retained(vello_hip_ctx *ctx, const float *transforms /* n x 6, nullable */, int transforms_is_device,
                               void *src_stream /* nullable hipStream_t */, const vello_hip_render_params *params, void *out_device,
                               size_t out_stride);
+/* vello_hip_render_retained with this frame's paints: a highlight on what vello_hip_pick found, a selection colour, a fade, a heat
+ * map whose colours a GPU op computes each frame -- without retaining the list again.  The reference seam is the one of
+ * vello_hip_render_instances_painted (Encoding::encode_brush per appended scene).  vello_hip_render_retained is this call with
+ * paints == NULL: the same frame, bit for bit, from the same kernels (no new kernel is launched), its draw data read from the
+ * retained bytes.
+ *   1. WHAT A PAINTED RETAINED FRAME IS.  Let R be the paints the list was retained with (KEEP everywhere if none), P this frame's
+ *      paints, X this frame's poses as rule 3 of vello_hip_render_retained defines them, and Q_i = P_i where P_i.flags ==
+ *      VELLO_HIP_PAINT_SOLID, else R_i.  The frame is vello_hip_render_instances_painted((fragment_i, X_i), Q, n), bit for bit in
+ *      every buffer and counter, view transform and viewport culling included.  VELLO_HIP_PAINT_KEEP therefore keeps what the
+ *      list was retained with, its retained paint included: a highlight is SOLID on one instance and KEEP on the rest.  A SOLID
+ *      paint on an instance whose fragment has no colour word changes nothing.  Colour words are the ones the rule at
+ *      vello_hip_render_instances_painted defines (DRAWTAG_FILL_COLOR, DRAWTAG_BLURRED_ROUNDED_RECT, per fragment), through the
+ *      masks kept since vello_hip_upload_fragments; a library that keeps no masks refuses a paint list, as the other painted
+ *      entry points do.
+ *   2. HOW THE FRAME'S COLOURS ARE MADE.  ONE kernel (k_instance_paints, a lane per draw-data word) writes the frame's draw-data
+ *      words into a per-buffer-set copy of the draw-data stream behind the retained bytes, at the head of the frame beside
+ *      k_instance_transforms; nothing is re-encoded and no other word is rewritten.  The kernels that read draw data (the draw
+ *      stage and coarse's preparation, in every launch form that holds them) are handed the copy in the stream's place, so
+ *      coarse's occlusion culling judges the frame's colours: an instance painted opaque this frame may occlude, painted
+ *      translucent it may not.  VELLO_HIP_BUF_SCENE shows the retained bytes as before -- the library's transforms and the
+ *      retained colours R, not P -- and VELLO_HIP_BUF_CONFIG the composed layout with the scene's own draw_data_base.  The copy
+ *      must be reachable with the scene pointer and a u32 word offset: a list whose retained bytes and copies together reach 2^32
+ *      words is refused with VELLO_HIP_E_INVALID when a painted frame is enqueued; its unpainted frames are served as before.
+ *   3. WHERE THE PAINTS COME FROM.  paints == NULL: an unpainted frame.  Host memory (paints_is_device == 0): n x 8 bytes, copied
+ *      through pinned memory during the call (`paints` may be reused on return); a flags value other than 0 or 1 is
+ *      VELLO_HIP_E_INVALID with vello_hip_last_error naming the instance, nothing is enqueued and the rotation stays where it
+ *      was.  Device memory (paints_is_device != 0): 4-byte aligned, n x 8 bytes in one allocation on the context's device
+ *      (anything else is refused in GPU builds, as for device poses); the host never reads it and does no per-instance work.  A
+ *      device paint with flags other than 0 or 1 is found by the kernel and the frame is discarded exactly like one with a NaN
+ *      device pose: the target untouched, VELLO_HIP_E_INVALID at vello_hip_sync, the next frame unaffected.  `src_stream` is legal
+ *      when at least one of the two sources is device memory: the frame waits for what has been enqueued on it so far, and
+ *      src_stream then waits for the last kernel of the frame that reads the caller's memory -- work enqueued there afterwards
+ *      may overwrite poses and paints.  With two host sources, or two NULL sources, src_stream must be NULL.
+ *   4. PAINTS BELONG TO THEIR FRAME.  Four frames in flight may show one list under four paint sets, and four pose sets, in four
+ *      targets.  An unpainted retained frame that follows a painted one on the same buffer set shows the retained colours.  The
+ *      retained bytes and the library's bytes are never modified.  vello_hip_run_stages after a painted retained frame goes on from
+ *      that frame's colour words and transform words as they are: neither the paints nor the poses are read again.  Every
+ *      refusal of vello_hip_render_retained applies.  A steady state of painted frames allocates no scene buffer
+ *      (vello_hip_scene_allocations unchanged): the room for the copies is made with the list.
+ *   5. Out of scope: alpha modulation; gradient, image and layer-alpha overrides; per-frame membership or order; pool estimation
+ *      for instance lists. */
+int vello_hip_render_retained_painted(vello_hip_ctx *ctx, const float *transforms /* n x 6, nullable */, int transforms_is_device,
+                                      const vello_hip_paint *paints /* n entries, nullable */, int paints_is_device,
+                                      void *src_stream /* nullable hipStream_t */, const vello_hip_render_params *params,
+                                      void *out_device, size_t out_stride);
 int vello_hip_release_retained(vello_hip_ctx *ctx);
 
 /* Hit testing: the topmost draw object, and the instance that owns it, under each of n points of the frame submitted last on the

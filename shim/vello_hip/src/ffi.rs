@@ -153,6 +153,7 @@ unsafe extern "C" {
     pub fn vello_hip_render_instances_painted(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, paints: *const vello_hip_paint, n: u32, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_retain_instances(ctx: *mut vello_hip_ctx, inst: *const vello_hip_instance, paints: *const vello_hip_paint, n: u32) -> c_int;
     pub fn vello_hip_render_retained(ctx: *mut vello_hip_ctx, transforms: *const f32, transforms_is_device: c_int, src_stream: *mut c_void, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
+    pub fn vello_hip_render_retained_painted(ctx: *mut vello_hip_ctx, transforms: *const f32, transforms_is_device: c_int, paints: *const vello_hip_paint, paints_is_device: c_int, src_stream: *mut c_void, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_release_retained(ctx: *mut vello_hip_ctx) -> c_int;
     pub fn vello_hip_pick(ctx: *mut vello_hip_ctx, points: *const f32, n: u32, points_is_device: c_int, src_stream: *mut c_void, out: *mut vello_hip_pick_hit, out_is_device: c_int) -> c_int;
     pub fn vello_hip_pick_ms(ctx: *mut vello_hip_ctx, ms_out: *mut f32) -> c_int;

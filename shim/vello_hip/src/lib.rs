@@ -287,6 +287,28 @@ impl HipRenderer {
         if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
     }
 
+    /// `vello_hip_render_retained_painted` with poses and this frame's paints in host memory, one of each per retained instance
+    /// (`None`: the rest poses / an unpainted frame).  A paint with `VELLO_HIP_PAINT_KEEP` keeps what the list was retained with.
+    pub fn render_retained_painted(&mut self, poses: Option<&[[f32; 6]]>, paints: Option<&[vello_hip_paint]>, target: *mut c_void, stride: usize,
+                                   params: &vello_hip_render_params) -> Result<(), Error> {
+        let poses_ptr = poses.map_or(core::ptr::null(), |p| p.as_ptr().cast::<f32>());
+        let paints_ptr = paints.map_or(core::ptr::null(), |p| p.as_ptr());
+        let rc = unsafe { vello_hip_render_retained_painted(self.ctx, poses_ptr, 0, paints_ptr, 0, core::ptr::null_mut(), params, target, stride) };
+        if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
+    }
+
+    /// `vello_hip_render_retained_painted` with poses and paints in device memory (`6 * n` floats and `2 * n` words on the context's
+    /// device, 4-byte aligned, either nullable), written by work on `src_stream` (a `hipStream_t`, nullable): the frame waits for
+    /// that work, the stream for the last kernel that reads them.
+    ///
+    /// # Safety
+    /// `poses` and `paints` must stay valid, and unchanged by anything but `src_stream`, until the frame has read them.
+    pub unsafe fn render_retained_painted_device(&mut self, poses: *const f32, paints: *const vello_hip_paint, src_stream: *mut c_void,
+                                                 target: *mut c_void, stride: usize, params: &vello_hip_render_params) -> Result<(), Error> {
+        let rc = vello_hip_render_retained_painted(self.ctx, poses, 1, paints, 1, src_stream, params, target, stride);
+        if rc == VELLO_HIP_OK { Ok(()) } else { Err(Self::error(self.ctx, rc, vello_hip_bump::default())) }
+    }
+
     /// `vello_hip_release_retained`.
     pub fn release_retained(&mut self) -> bool {
         unsafe { vello_hip_release_retained(self.ctx) == VELLO_HIP_OK }

@@ -110,6 +110,7 @@ def load_library():
     sig("vello_hip_render_instances_painted", i32, [vp, vp, vp, u32, c.POINTER(RenderParamsStruct), vp, sz])
     sig("vello_hip_retain_instances", i32, [vp, vp, vp, u32])
     sig("vello_hip_render_retained", i32, [vp, vp, i32, vp, c.POINTER(RenderParamsStruct), vp, sz])
+    sig("vello_hip_render_retained_painted", i32, [vp, vp, i32, vp, i32, vp, c.POINTER(RenderParamsStruct), vp, sz])
     sig("vello_hip_release_retained", i32, [vp])
     sig("vello_hip_pick", i32, [vp, vp, u32, i32, vp, vp, i32])
     sig("vello_hip_pick_constant", u32, [i32])

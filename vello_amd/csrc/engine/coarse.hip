@@ -821,7 +821,7 @@ void launch_coarse(const Frame &f, hipStream_t s, hipEvent_t *mid) {
     uint32_t n_bit_blocks = (uint32_t)(((uint64_t)f.cfg.tiles_size + 256u * 8u - 1u) / (256u * 8u));
     if (n_bit_blocks > 2048u) n_bit_blocks = 2048u;
     if (n_bit_blocks < 1u) n_bit_blocks = 1u;
-    hipLaunchKernelGGL(k_coarse_prep, dim3(n_el_blocks + n_bit_blocks), dim3(256), 0, s, f.cfg, n_el_blocks, f.scene, f.draw_monoids,
+    hipLaunchKernelGGL(k_coarse_prep, dim3(n_el_blocks + n_bit_blocks), dim3(256), 0, s, dd_config(f), n_el_blocks, f.scene, f.draw_monoids,
                        f.info_bin_data, f.paths, f.tiles, f.bump(), f.coarse_el, f.tile_bits);
     if (mid) (void)hipEventRecord(mid[0], s);
     const uint32_t n_wg = ((wb * hb + COARSE_GRID_BINS - 1u) / COARSE_GRID_BINS) * COARSE_GRID_BINS * 4u;

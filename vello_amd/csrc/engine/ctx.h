@@ -57,6 +57,12 @@ struct SceneSlot {
     // the bytes were composed from the library's fragments (vello_hip_render_instances, vello_hip_retain_instances): ramps are the
     // shared slot's
     bool composed = false;
+    // The retained slot only: the draw-data words of PAINTED retained frames (vello_hip_render_retained_painted, Frame::dd_base) --
+    // `dd_sets` copies (a lane each) of `dd_set_words` words, the draw-data stream's length, from word `dd_at` of the scene's
+    // allocation: behind the transform copies, in the same tail (view_cap_bytes covers both).  dd_sets == 0: the slot has none
+    // (every other slot; a list so large that the copies would be out of a u32 word offset's reach -- it takes no paints).
+    size_t dd_at = 0;
+    uint32_t dd_sets = 0, dd_set_words = 0;
 };
 // A fragment of the library as the host keeps it: where its range begins in each stream and how long it is -- in the units of
 // ComposeArgs (bytes for tags, words otherwise) -- what the composed layout and fine's specialisation need of its draw tags, and
@@ -100,6 +106,15 @@ struct Lane {
     // ctx::retained.generation of the list whose composed transform words the lane's copy holds (0: none): vello_hip_run_stages
     // after a retained frame goes on from them
     uint64_t posed_generation = 0;
+    // vello_hip_render_retained_painted: the frame's paints when they came from the host (n x 2 words, copied on the lane's stream) ...
+    DevBuf paints;
+    // ... and where the frame's k_instance_paints reads them: `paints`, the caller's device memory, or null for an unpainted frame
+    const uint32_t *paint_src = nullptr;
+    bool paint_check = false;           // the caller's device memory: the host has not seen the paints, the kernel tests their flags
+    // (both belong to the frame being entered and are cleared with the pose source)
+    // ctx::retained.generation of the list whose painted draw-data words the lane's copy holds BECAUSE the lane's latest retained
+    // frame was a painted one (0: it was not): vello_hip_run_stages after a painted frame goes on from them
+    uint64_t painted_generation = 0;
     DevBuf front_sync;                // k_front's grid-barrier counter (zeroed once, when allocated)
     uint32_t front_sync_value = 0;    // ... and its value once every launch enqueued so far has run
     struct EvPair {
@@ -157,12 +172,18 @@ struct vello_hip_ctx {
     // add up to 2^32 words or more: such a library takes no paints.
     vk::DevBuf frag_masks;
     bool have_masks = false;
+    // ... and the host's copy of the bit array (FragmentInfo::mask_bit indexes it): vello_hip_retain_instances builds the list's
+    // per-word table from it
+    std::vector<uint32_t> frag_masks_host;
     // vello_hip_retain_instances: the composed scene of ONE instance list, kept across frames (transform entries: the library's,
     // verbatim; a transform copy per lane behind its bytes, as the shared slot has), the instance that owns each transform entry
     // ([n_xf] u32) and the rest poses ([n][6] f32).  Dropped with the fragment table.
     vk::SceneSlot retained;
     vk::DevBuf retained_owner, retained_rest;
     vk::DevBuf retained_prefix;  // [n + 1] the list's draw-tag prefix (ComposeArgs::table's third row): vello_hip_pick's owner search
+    // [draw-data words] owner | colour word << 31 (InstancePaintArgs::map): what k_instance_paints reads.  Built with the list when
+    // the library keeps masks (have_masks); a list of a library without them takes no paints.
+    vk::DevBuf retained_ddmap;
     uint32_t retained_n = 0;
     bool have_retained = false;
     hipEvent_t pose_mark = nullptr;  // orders a retained frame's pose kernel, and vello_hip_pick's read of device points, against the caller's src_stream
@@ -234,6 +255,7 @@ int alloc_lane_scene(vello_hip_ctx *c, Lane &l, const SceneSlot &sc);
 // frames.hip
 int check_target(vello_hip_ctx *c, const vello_hip_render_params *p, const void *out, size_t out_stride, bool device);
 int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
+int paint_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
 int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, void *out_device, size_t out_stride, Frame &f, bool upload_cfg);
 int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int last);
 // scenes.hip

@@ -164,6 +164,18 @@ struct Frame {
     hipStream_t pose_stream;
     hipEvent_t pose_mark;
     bool pose_check;
+    // The draw-data words the draw stage and k_coarse_prep read: scene[(u32)(dd_base + offset)].  The scene's own stream
+    // (dd_base == cfg.layout.draw_data_base) for every frame but a PAINTED frame of the retained list
+    // (vello_hip_render_retained_painted): there it is the lane's copy of the stream behind the retained bytes and the transform
+    // copies, which k_instance_paints fills at the head of the frame from the list's per-word table (dd_map) and this frame's
+    // paints (paint_words: [n][2] (flags, rgba); null: the copy already holds the frame's words, nothing is launched --
+    // vello_hip_run_stages after a painted frame).  paint_check: the paints are the caller's device memory, which the host has
+    // not read -- the kernel tests their flags.  The readers are handed a Config whose layout.draw_data_base is dd_base
+    // (xf_config, dd_config) and are the same code whether the frame is painted or not.
+    uint32_t dd_base;
+    const uint32_t *dd_map;
+    const uint32_t *paint_words;
+    bool paint_check;
     Control *control;
     uint32_t *heavy_list;   // flatten: tag indices that need the Euler-spiral / stroker path
     uint32_t *arc_items;    // flatten: 16 words per round join / cap arc that a stroke workgroup leaves to the heavy code
@@ -215,10 +227,18 @@ struct Frame {
     Bump *bump() const { return &control->bump; }
 };
 
-// the Config of the kernels that read transforms (flatten's, the draw stage's): the frame's, with the transform words' base
+// the Config of the kernels that read transforms (flatten's, the draw stage's): the frame's, with the transform words' base -- and
+// the draw-data words' base, which the draw stage reads through the same Config (an unpainted frame's: the scene's own)
 inline Config xf_config(const Frame &f) {
     Config c = f.cfg;
     c.layout.transform_base = f.xf_base;
+    c.layout.draw_data_base = f.dd_base;
+    return c;
+}
+// the Config of k_coarse_prep, which reads draw data and no transforms: the frame's, with the draw-data words' base
+inline Config dd_config(const Frame &f) {
+    Config c = f.cfg;
+    c.layout.draw_data_base = f.dd_base;
     return c;
 }
 // k_view_transforms (scene_ops.hip): fills the frame's composed transform words; launched at the head of a frame that has a view
@@ -238,6 +258,23 @@ struct InstanceXfArgs {
 // fills the composed transform words of a retained frame; check_poses: the frame's control block has been cleared on `s` and the
 // pathtag scan has not been enqueued yet
 void launch_instance_transforms(const Frame &f, bool check_poses, hipStream_t s);
+// k_instance_paints (scene_ops.hip): what it is handed by value.  Word w of `out` is the retained scene's draw-data word w, or the
+// rgba of this frame's paint of the instance that owns it where the word is a colour word and that paint is SOLID: the frame's
+// draw-data words.
+//   map: [n_words] owner | is_colour_word << 31 per draw-data word of the retained scene (n <= 2^32 / 6 instances: bit 31 is free);
+//        owners do not decrease along the stream.
+constexpr uint32_t DD_MAP_COLOUR = 0x80000000u;
+struct InstancePaintArgs {
+    const uint32_t *scene;   // the retained scene: its colour words are the ones the list was retained with
+    const uint32_t *map;     // [n_words]
+    const uint32_t *paints;  // [n][2] this frame's (flags, rgba), 4-byte aligned
+    uint32_t *out;           // word 0 of the lane's copy
+    uint32_t *failed;        // nullable: &control->bump.failed, ORed with FAILED_SCENE when a paint's flags are neither KEEP nor SOLID
+    uint32_t draw_data_base, n_words, n;
+};
+// fills the draw-data words of a painted retained frame (Frame::paint_words is set); check_paints: the frame's control block has
+// been cleared on `s` and the pathtag scan has not been enqueued yet
+void launch_instance_paints(const Frame &f, bool check_paints, hipStream_t s);
 
 void launch_pathtag_scan(const Frame &f, hipStream_t s);
 // (mid: when not null, an event is recorded behind every kernel of the stage but the last: per-KERNEL times of a stage of

@@ -131,6 +131,20 @@ int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &ba
     return 0;
 }
 
+// Where lane l's copy of the retained list's draw-data words lies, in words from the scene's start (SceneSlot::dd_at): what a
+// painted retained frame reads in the stream's place.  VELLO_HIP_E_INVALID for a list so large that the copies are out of a u32
+// offset's reach (it was given none); asked before the rotation moves, as view_base is.
+int paint_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base) {
+    const size_t set = (size_t)(&l - c->lanes.data());
+    const uint64_t at = (uint64_t)sc.dd_at + (uint64_t)set * sc.dd_set_words;
+    if (set >= sc.dd_sets || at + sc.dd_set_words > 0xffffffffull) {
+        c->last_error = "the retained list is too large for per-frame paints (its bytes and copies must lie within 2^32 words of its start)";
+        return VELLO_HIP_E_INVALID;
+    }
+    base = (uint32_t)at;
+    return 0;
+}
+
 // The target contract of include/vello_hip.h (at vello_hip_render_resident).  fine stores dwords at output + y * stride and takes the
 // stride as a u32: a device target that is not 4-aligned, rows that overlap or a stride of 2^32 and more would corrupt silently.
 // Every entry point that takes a target asks before it uploads, rotates or enqueues anything.
@@ -217,6 +231,18 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
     f.pose_stream = f.retained ? l.pose_stream : nullptr;
     f.pose_mark = c->pose_mark;
     f.pose_check = f.retained && l.pose_check;
+    // its draw-data words: the retained stream's -- or, a painted frame's (the entry point has set the lane's paint source) and a
+    // vello_hip_run_stages' after one (the lane's copy holds that frame's words), the lane's copy
+    f.dd_base = sc.layout.draw_data_base;
+    f.dd_map = nullptr;
+    f.paint_words = nullptr;
+    f.paint_check = false;
+    if (f.retained && (l.paint_src || l.painted_generation == sc.generation)) {
+        if ((r = paint_base(c, sc, l, f.dd_base))) return r;
+        f.dd_map = (const uint32_t *)c->retained_ddmap.ptr;
+        f.paint_words = l.paint_src;
+        f.paint_check = l.paint_src && l.paint_check;
+    }
     f.control = (Control *)l.zero_region.ptr;
     f.zero_bytes = (uint32_t)sc.zero_bytes;
     f.front_sync = (uint32_t *)l.front_sync.ptr;
@@ -345,16 +371,24 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
     // device memory (pose_check; such a frame begins with the pathtag scan) the frame's zero fill comes first, here instead of in
     // that stage, so that the kernel can raise FAILED_SCENE over a pose that is not finite: behind the fill, ahead of the scan
     // (`zeroed`: the stage then neither clears nor has k_front clear).  Poses the host has tested keep the stage's own fill.
+    // A painted frame: k_instance_paints beside it, which fills the lane's copy of the draw-data words the draw stage and coarse
+    // read; device paints (paint_check) are tested by that kernel the way device poses are, behind the same early zero fill.
     bool zeroed = false;
-    if (f.retained && f.pose_words && first <= VELLO_HIP_STAGE_DRAW_SCAN && last >= VELLO_HIP_STAGE_FLATTEN) {
-        if (f.pose_check && first == VELLO_HIP_STAGE_PATHTAG_SCAN) {
+    if (f.retained && (f.pose_words || f.paint_words) && first <= VELLO_HIP_STAGE_DRAW_SCAN && last >= VELLO_HIP_STAGE_FLATTEN) {
+        if ((f.pose_check || f.paint_check) && first == VELLO_HIP_STAGE_PATHTAG_SCAN) {
             HIP_TRY(c, hipMemsetAsync(l.zero_region.ptr, 0, slot_of(c, l).zero_bytes, st));
             zeroed = true;
         }
-        launch_instance_transforms(f, zeroed, st);
-        HIP_TRY(c, hipGetLastError());
-        l.posed_generation = c->retained.generation;
-        if (f.pose_stream) {  // the caller's stream may overwrite the poses once this kernel has read them
+        if (f.pose_words) {
+            launch_instance_transforms(f, zeroed && f.pose_check, st);
+            HIP_TRY(c, hipGetLastError());
+            l.posed_generation = c->retained.generation;
+        }
+        if (f.paint_words) {
+            launch_instance_paints(f, zeroed && f.paint_check, st);
+            HIP_TRY(c, hipGetLastError());
+        }
+        if (f.pose_stream) {  // the caller's stream may overwrite poses and paints once these kernels have read them
             HIP_TRY(c, hipEventRecord(f.pose_mark, st));
             HIP_TRY(c, hipStreamWaitEvent(f.pose_stream, f.pose_mark, 0));
         }
@@ -478,10 +512,12 @@ int vello_hip_render_resident(vello_hip_ctx *c, const vello_hip_render_params *p
     return enter_frame(c, params, out_device, out_stride, true, last, set_up, no_step, no_step);
 }
 
-// A frame of the retained instance list under this frame's poses.  Everything that can refuse the frame is asked before the lane
-// is taken; what the host does per frame does not depend on the list's length unless the poses are the host's own.
-int vello_hip_render_retained(vello_hip_ctx *c, const float *transforms, int transforms_is_device, void *src_stream,
-                              const vello_hip_render_params *params, void *out_device, size_t out_stride) {
+// A frame of the retained instance list under this frame's poses and paints.  Everything that can refuse the frame is asked before
+// the lane is taken; what the host does per frame does not depend on the list's length unless poses or paints are the host's own.
+// Without paints this is vello_hip_render_retained as it was: the same checks, the same copies, the same launches.
+int vello_hip_render_retained_painted(vello_hip_ctx *c, const float *transforms, int transforms_is_device, const vello_hip_paint *paints,
+                                      int paints_is_device, void *src_stream, const vello_hip_render_params *params, void *out_device,
+                                      size_t out_stride) {
     if (!c || !params) return VELLO_HIP_E_INVALID;
     auto refuse = [&](const std::string &why) {
         c->last_error = "render_retained: " + why;
@@ -489,42 +525,63 @@ int vello_hip_render_retained(vello_hip_ctx *c, const float *transforms, int tra
     };
     if (!c->have_retained || !c->retained.resident) return refuse("no retained instance list (vello_hip_retain_instances)");
     const uint32_t n = c->retained_n;
-    const size_t pose_bytes = (size_t)n * 24u;
+    const size_t pose_bytes = (size_t)n * 24u, paint_bytes = (size_t)n * sizeof(vello_hip_paint);
     const bool device = transforms != nullptr && transforms_is_device != 0;
-    if (src_stream && !device) return refuse("src_stream goes with poses in device memory");
+    const bool paints_device = paints != nullptr && paints_is_device != 0;
+    if (paints && !c->have_masks)
+        return refuse("the fragments' draw_data ranges add up to 2^32 words or more: the library takes no paints");
+    if (src_stream && !device && !paints_device) return refuse("src_stream goes with poses or paints in device memory");
     if (transforms && !device)
         for (uint32_t i = 0; i < n; i++)
             for (int k = 0; k < 6; k++) {
                 const float v = transforms[(size_t)i * 6u + k];
                 if (!(v - v == 0.0f)) return refuse("instance " + std::to_string(i) + ": the pose has an entry that is not finite");
             }
-    if (device) {
-        if ((reinterpret_cast<uintptr_t>(transforms) & 3u) != 0u) return refuse("the address of device poses is not a multiple of 4");
+    if (paints && !paints_device)
+        for (uint32_t i = 0; i < n; i++)
+            if (paints[i].flags != VELLO_HIP_PAINT_KEEP && paints[i].flags != VELLO_HIP_PAINT_SOLID)
+                return refuse("instance " + std::to_string(i) + ": paint flags " + std::to_string(paints[i].flags) + " (VELLO_HIP_PAINT_KEEP or _SOLID)");
+    // a source in device memory: 4-byte aligned, and -- GPU builds -- every byte the kernel reads lies in one allocation in device
+    // memory of this context's device (vello_hip_copy_images_device)
+    const auto check_device = [&](const void *ptr, size_t bytes, const char *what) -> int {
+        if ((reinterpret_cast<uintptr_t>(ptr) & 3u) != 0u) return refuse(std::string("the address of device ") + what + " is not a multiple of 4");
 #ifndef VELLO_SIMT_EMU
-        // every byte the kernel reads lies in one allocation in device memory of this context's device (vello_hip_copy_images_device)
         if (n != 0u) {
             hipDeviceptr_t base = nullptr;
             size_t size = 0;
             hipPointerAttribute_t attr{};
-            hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<float *>(transforms));
+            hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) const_cast<void *>(ptr));
             if (e == hipSuccess) e = hipPointerGetAttributes(&attr, base);
             (void)hipGetLastError();  // a host address is an error here: do not leave it for the next launch check
             if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != c->device)
-                return refuse("the poses are not device memory of device " + std::to_string(c->device));
-            if ((uint64_t)(uintptr_t)transforms + pose_bytes > (uint64_t)(uintptr_t)base + size)
-                return refuse("the poses run past the end of their allocation");
+                return refuse(std::string("the ") + what + " are not device memory of device " + std::to_string(c->device));
+            if ((uint64_t)(uintptr_t)ptr + bytes > (uint64_t)(uintptr_t)base + size)
+                return refuse(std::string("the ") + what + " run past the end of their allocation");
         }
+#else
+        (void)bytes;
 #endif
-    }
+        return 0;
+    };
     int r;
+    if (device && (r = check_device(transforms, pose_bytes, "poses"))) return r;
+    if (paints_device && (r = check_device(paints, paint_bytes, "paints"))) return r;
     if ((r = check_target(c, params, out_device, out_stride, true))) return r;
     {
         Config probe;  // (what prepare_frame would refuse, asked before the lane changes its scene)
         if ((r = configure(c, c->retained, params, probe))) return r;
     }
     HIP_TRY(c, hipSetDevice(c->device));
+    Lane &lane = c->lanes[c->next_lane % c->n_active];  // (the lane enter_frame takes)
+    if (paints) {
+        uint32_t probe;  // (likewise: the lane's copy of the draw-data words must be within reach)
+        if ((r = paint_base(c, c->retained, lane, probe))) return r;
+    }
     if (src_stream && !c->pose_mark) HIP_TRY(c, hipEventCreateWithFlags(&c->pose_mark, hipEventDisableTiming));
+    // host sources cross in ONE pinned block: the poses, then the paints
+    const size_t host_pose_bytes = transforms && !device ? pose_bytes : 0u, host_paint_bytes = paints && !paints_device ? paint_bytes : 0u;
     Staging *st = nullptr;
+    const uint64_t painted_was = lane.painted_generation;
     const auto set_up = [&](Lane &l, bool &new_scene) -> int {
         new_scene = l.which != LaneScene::Retained;  // (else: sized when the list was retained, or by the lane's earlier frame of it)
         if (!new_scene) return 0;
@@ -533,20 +590,35 @@ int vello_hip_render_retained(vello_hip_ctx *c, const float *transforms, int tra
         return 0;
     };
     const auto staged = [&](Lane &l) -> int {
-        if (transforms && !device) {
-            if (int sr = acquire_staging(c, pose_bytes, st)) return sr;
+        const bool host_poses = transforms && !device, host_paints = paints && !paints_device;
+        if (host_poses || host_paints)
+            if (int sr = acquire_staging(c, host_pose_bytes + host_paint_bytes, st)) return sr;
+        if (host_poses)
             if (int sr = ensure(c, l.poses, pose_bytes)) return sr;
-        }
+        if (host_paints)
+            if (int sr = ensure(c, l.paints, paint_bytes)) return sr;
         l.pose_src = !transforms ? nullptr : device ? reinterpret_cast<const uint32_t *>(transforms) : (const uint32_t *)l.poses.ptr;
         l.pose_stream = (hipStream_t)src_stream;
         l.pose_check = device;
+        l.paint_src = !paints ? nullptr : paints_device ? reinterpret_cast<const uint32_t *>(paints) : (const uint32_t *)l.paints.ptr;
+        l.paint_check = paints_device;
+        // (prepare_frame picks the lane's copy of the draw-data words for a painted frame, the retained stream otherwise)
+        l.painted_generation = paints ? c->retained.generation : 0u;
         return 0;
     };
+    bool entered = false;
     const auto enqueue = [&](Lane &l) -> int {
+        entered = true;
         c->cfg_unsent = true;  // (as an instance frame: VELLO_HIP_BUF_CONFIG gets the Config when it is next read or written)
-        if (st && pose_bytes) {
-            std::memcpy(st->host, transforms, pose_bytes);
-            HIP_TRY(c, hipMemcpyAsync(l.poses.ptr, st->host, pose_bytes, hipMemcpyHostToDevice, l.stream));
+        if (st) {
+            if (host_pose_bytes) {
+                std::memcpy(st->host, transforms, host_pose_bytes);
+                HIP_TRY(c, hipMemcpyAsync(l.poses.ptr, st->host, host_pose_bytes, hipMemcpyHostToDevice, l.stream));
+            }
+            if (host_paint_bytes) {
+                std::memcpy((char *)st->host + host_pose_bytes, paints, host_paint_bytes);
+                HIP_TRY(c, hipMemcpyAsync(l.paints.ptr, (char *)st->host + host_pose_bytes, host_paint_bytes, hipMemcpyHostToDevice, l.stream));
+            }
             HIP_TRY(c, hipEventRecord(st->done, l.stream));
             st->busy = true;
         }
@@ -556,13 +628,20 @@ int vello_hip_render_retained(vello_hip_ctx *c, const float *transforms, int tra
         }
         return 0;
     };
-    Lane &lane = c->lanes[c->next_lane % c->n_active];  // (the lane enter_frame takes)
     r = enter_frame(c, params, out_device, out_stride, false, VELLO_HIP_STAGE_FINE, set_up, staged, enqueue);
-    // the poses belonged to this frame, enqueued or refused: the lane keeps neither the caller's memory nor the caller's stream
+    // poses and paints belonged to this frame, enqueued or refused: the lane keeps neither the caller's memory nor the caller's stream
     lane.pose_src = nullptr;
     lane.pose_stream = nullptr;
     lane.pose_check = false;
+    lane.paint_src = nullptr;
+    lane.paint_check = false;
+    if (!entered) lane.painted_generation = painted_was;  // (refused: the lane's latest frame is still the one before)
     return r;
+}
+
+int vello_hip_render_retained(vello_hip_ctx *c, const float *transforms, int transforms_is_device, void *src_stream,
+                              const vello_hip_render_params *params, void *out_device, size_t out_stride) {
+    return vello_hip_render_retained_painted(c, transforms, transforms_is_device, nullptr, 0, src_stream, params, out_device, out_stride);
 }
 
 int vello_hip_run_stages(vello_hip_ctx *c, const vello_hip_render_params *params, int first, int last) {

@@ -1,4 +1,5 @@
-// Device-side operations on scene data outside the pipeline's stages: atlas copies, the view's transform words, scene composition.
+// Device-side operations on scene data outside the pipeline's stages: atlas copies, the view's transform words, a retained list's
+// per-frame transform and draw-data words, scene composition.
 #include "engine.h"
 
 namespace vk {
@@ -155,6 +156,51 @@ void launch_instance_transforms(const Frame &f, bool check_poses, hipStream_t s)
     // (n * 6 and n_xf * 6 are below 2^32: vello_hip_retain_instances)
     const uint32_t lanes = a.n_xf + 1u > (check_poses ? a.n : 0u) ? a.n_xf + 1u : a.n;
     hipLaunchKernelGGL(k_instance_transforms, dim3((lanes + 255u) / 256u), dim3(256), 0, s, a);
+}
+
+// k_instance_paints: the draw-data words of a PAINTED frame of the retained instance list (vello_hip_render_retained_painted; the
+// arguments are in engine.h), a lane per draw-data word of the retained scene, beside k_instance_transforms at the head of the frame.
+// Word w of `out` -- the lane's copy of the stream, which the draw stage and k_coarse_prep then read in the stream's place -- is the
+// retained word, or paints[owner].rgba where the word is a colour word and its owner's paint is SOLID.  Which instance owns a word,
+// and whether it is a colour word, is one entry of a table the host built when the list was retained (owner | colour << 31): a lane
+// reads it with its neighbours' (one coalesced dword load a wave), as it reads the retained word and writes the copy.  Owners do not
+// decrease along the stream, so the paints a wave reads are those of a run of instances: lanes of one instance read the same two
+// words, and a wave of one-word fragments reads 512 consecutive bytes.  Only colour words read a paint at all.  Dword accesses
+// throughout: paints and streams are 4-byte aligned only.  No LDS: nothing is shared beyond what the cache holds.  A wholesale
+// copy rather than a list of the colour words alone: the readers take ONE base for the whole stream, and the non-colour words of a
+// symbol map are a few words an instance.
+// Where the paints are the caller's device memory (Frame::paint_check) the same grid tests them: lane i < n tests paint i, whether
+// or not instance i owns a word, and a flags value other than KEEP or SOLID ORs FAILED_SCENE into the frame's bump.failed -- that
+// launch sits behind the frame's zero fill and ahead of its pathtag scan, as k_instance_transforms' test of device poses does.
+// `failed` is null for host paints, which the host has tested: no test, and the grid covers the words only.
+__global__ void __launch_bounds__(256) k_instance_paints(InstancePaintArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (a.failed != nullptr && i < a.n) {
+        if (a.paints[(size_t)i * 2u] > PAINT_SOLID) atomicOr(a.failed, FAILED_SCENE);
+    }
+    if (i >= a.n_words) return;
+    const uint32_t m = a.map[i];
+    uint32_t v = a.scene[(size_t)a.draw_data_base + i];
+    if ((m & DD_MAP_COLOUR) != 0u) {
+        const uint32_t *paint = a.paints + (size_t)(m & ~DD_MAP_COLOUR) * 2u;  // owner < n: the host built the table from the list it retained
+        if (paint[0] == PAINT_SOLID) v = paint[1];
+    }
+    a.out[i] = v;
+}
+
+void launch_instance_paints(const Frame &f, bool check_paints, hipStream_t s) {
+    InstancePaintArgs a{};
+    a.scene = f.scene;
+    a.map = f.dd_map;
+    a.paints = f.paint_words;
+    a.out = const_cast<uint32_t *>(f.scene) + f.dd_base;
+    a.failed = check_paints ? &f.control->bump.failed : nullptr;
+    a.draw_data_base = f.cfg.layout.draw_data_base;
+    a.n_words = f.cfg.layout.transform_base - f.cfg.layout.draw_data_base;
+    a.n = f.n_instances;
+    const uint32_t lanes = a.n_words > (check_paints ? a.n : 0u) ? a.n_words : (check_paints ? a.n : 0u);
+    if (lanes == 0u) return;  // (no draw data and nothing to test)
+    hipLaunchKernelGGL(k_instance_paints, dim3((lanes + 255u) / 256u), dim3(256), 0, s, a);
 }
 
 // k_compose_scene: a frame's packed scene written from instances of the library's fragments (vello_hip_render_instances; the contract is

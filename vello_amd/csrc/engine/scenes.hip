@@ -55,9 +55,22 @@ int size_slot(vello_hip_ctx *c, SceneSlot &sc, const vello_hip_layout &L, size_t
     // ... and, behind them, room for the composed transform words of frames with a view (SceneSlot::view_at)
     const uint32_t set_words = ((L.style_base - L.transform_base) / 6u + 1u) * 6u;
     const uint32_t sets = &sc == &c->shared || &sc == &c->retained ? MAX_LANES : 1u;
-    if ((r = ensure_scene(c, sc, scene_len + 64, (size_t)set_words * sets * 4u))) return r;
+    // ... and, the retained slot only, behind those a copy per lane of the draw-data stream for painted frames (SceneSlot::dd_at) --
+    // unless the copies would lie beyond a u32 word offset from the scene's start: such a list takes no paints and gets no room
+    const size_t xf_tail_words = (size_t)set_words * sets;
+    const uint32_t dd_words = L.transform_base - L.draw_data_base;
+    uint32_t dd_sets = 0u;
+    if (&sc == &c->retained) {
+        const size_t visible = sc.scene.size > scene_len + 64 ? sc.scene.size : scene_len + 64;  // (what ensure_scene settles on)
+        const uint64_t reach = (uint64_t)((visible + 15u) / 4u) + xf_tail_words + (uint64_t)dd_words * MAX_LANES;
+        if (reach <= 0xffffffffull) dd_sets = MAX_LANES;
+    }
+    if ((r = ensure_scene(c, sc, scene_len + 64, (xf_tail_words + (size_t)dd_words * dd_sets) * 4u))) return r;
     sc.view_sets = sets;
     sc.view_set_words = set_words;
+    sc.dd_at = sc.view_at + xf_tail_words;
+    sc.dd_sets = dd_sets;
+    sc.dd_set_words = dd_words;
     sc.layout = L;
     sc.scene_len = scene_len;
     uint32_t n_path_tags = (L.path_data_base - L.path_tag_base) * 4u;
@@ -339,6 +352,7 @@ int vello_hip_upload_scene(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
     if ((r = sync_all(c))) return r;
     c->have_fragments = false;  // (vello_hip_upload_fragments sets its table once the scene is resident)
     c->have_masks = false;
+    c->frag_masks_host.clear();
     c->fragments.clear();
     drop_retained(c);
     if ((r = load_slot(c, c->shared, c->lanes[0].stream, scene, scene_len, layout, ramps, n_ramps))) return r;
@@ -359,6 +373,7 @@ int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t sc
     c->shared.resident = false;
     c->have_fragments = false;
     c->have_masks = false;
+    c->frag_masks_host.clear();
     c->fragments.clear();
     drop_retained(c);
     if (n_frags > 0u && !frags) {
@@ -371,7 +386,11 @@ int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t sc
     // [n_frags] bit offsets, then the colour-word masks (ctx::frag_masks); bit offsets stay within u32 or no masks are kept
     std::vector<uint32_t> masks;
     uint64_t mask_bits = 0;
-    bool keep_masks = true;
+    // (known before the walk: a library that takes no paints never has its bit array built)
+    uint64_t total_bits = 0;
+    for (uint32_t i = 0; i < n_frags; i++)
+        if (frags[i].draw_data[0] <= frags[i].draw_data[1]) total_bits += frags[i].draw_data[1] - frags[i].draw_data[0];
+    bool keep_masks = total_bits <= 0xffffffffull;
     for (uint32_t i = 0; i < n_frags; i++) {
         if ((r = check_fragment(c, scene, scene_len, *layout, frags[i], i, infos[i], keep_masks ? &masks : nullptr, mask_bits))) return r;
         mask_bits += infos[i].len[3];
@@ -413,6 +432,7 @@ int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t sc
     c->fragments = std::move(infos);
     c->have_fragments = true;
     c->have_masks = keep_masks;
+    if (keep_masks) c->frag_masks_host = std::move(masks);  // (vello_hip_upload_scene above cleared it)
     return VELLO_HIP_OK;
 }
 
@@ -517,11 +537,25 @@ int vello_hip_retain_instances(vello_hip_ctx *c, const vello_hip_instance *inst,
         at += fi.len[4];
         std::memcpy(&rest[(size_t)i * 6u], inst[i].transform, 24);
     }
+    // the per-word table of k_instance_paints: for every draw-data word its instance, and bit 31 where the fragment's mask has the
+    // word as a colour word (n <= 2^32 / 6 leaves the bit free).  A library without masks takes no paints: no table.
+    std::vector<uint32_t> ddmap(c->have_masks ? p.len[3] : 0u);
+    if (c->have_masks) {
+        size_t w = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const FragmentInfo &fi = c->fragments[inst[i].fragment];
+            for (uint32_t k = 0; k < fi.len[3]; k++) {
+                const uint32_t bit = fi.mask_bit + k;
+                ddmap[w++] = i | (((c->frag_masks_host[bit >> 5] >> (bit & 31u)) & 1u) != 0u ? DD_MAP_COLOUR : 0u);
+            }
+        }
+    }
     DevBuf table_dev;  // (freed on the way out: the list is composed once)
     if ((r = ensure(c, table_dev, table.size() * 4u))) return r;
     if ((r = ensure(c, c->retained_owner, owner.size() * 4u))) return r;
     if ((r = ensure(c, c->retained_rest, rest.size() * 4u))) return r;
     if ((r = ensure(c, c->retained_prefix, ((size_t)n + 1u) * 4u))) return r;
+    if ((r = ensure(c, c->retained_ddmap, ddmap.size() * 4u))) return r;
     hipStream_t st = c->lanes[0].stream;
     HIP_TRY(c, hipMemcpy(table_dev.ptr, table.data(), table.size() * 4u, hipMemcpyHostToDevice));
     if ((r = launch_compose(c, p, n, paints != nullptr, (const uint32_t *)table_dev.ptr, (uint32_t *)sc.scene.ptr, st))) return r;
@@ -529,6 +563,7 @@ int vello_hip_retain_instances(vello_hip_ctx *c, const vello_hip_instance *inst,
     if (!xf.empty()) HIP_TRY(c, hipMemcpy((uint32_t *)sc.scene.ptr + p.layout.transform_base, xf.data(), xf.size() * 4u, hipMemcpyHostToDevice));
     if (!owner.empty()) HIP_TRY(c, hipMemcpy(c->retained_owner.ptr, owner.data(), owner.size() * 4u, hipMemcpyHostToDevice));
     if (!rest.empty()) HIP_TRY(c, hipMemcpy(c->retained_rest.ptr, rest.data(), rest.size() * 4u, hipMemcpyHostToDevice));
+    if (!ddmap.empty()) HIP_TRY(c, hipMemcpy(c->retained_ddmap.ptr, ddmap.data(), ddmap.size() * 4u, hipMemcpyHostToDevice));
     // (the table's third row: the exclusive prefix of the instances' draw-tag counts, n + 1 entries)
     HIP_TRY(c, hipMemcpy(c->retained_prefix.ptr, table.data() + 2u * ((size_t)n + 1u), ((size_t)n + 1u) * 4u, hipMemcpyHostToDevice));
     // the lanes that showed the list this one replaces: their scene-dependent buffers must fit the new one
@@ -545,13 +580,14 @@ int vello_hip_release_retained(vello_hip_ctx *c) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = sync_all(c)) return r;
     drop_retained(c);
-    for (DevBuf *b : {&c->retained.scene, &c->retained_owner, &c->retained_rest, &c->retained_prefix}) {
+    for (DevBuf *b : {&c->retained.scene, &c->retained_owner, &c->retained_rest, &c->retained_prefix, &c->retained_ddmap}) {
         if (b->ptr) HIP_TRY(c, hipFree(b->ptr));
         b->ptr = nullptr;
         b->size = 0;
     }
     c->retained.view_cap_bytes = 0;
     c->retained.view_sets = 0;
+    c->retained.dd_sets = 0;
     return VELLO_HIP_OK;
 }
 

@@ -479,13 +479,18 @@ class Engine:
         self._retained_n = len(inst)
 
     def render_retained(self, width, height, base_color, aa, transforms=None, out=None, out_stride=None, src_stream=None,
-                        transforms_is_device=False):
+                        transforms_is_device=False, paints=None, paints_is_device=False):
         """vello_hip_render_retained: one frame of the retained list under this frame's poses, enqueued like render_instances.
         `transforms`: None (the rest poses), an (n, 6) float32 numpy array (host memory: copied during the call), or poses in device
         memory -- a float32 tensor of n * 6 elements on the engine's GPU, or its address as an int -- which the host never reads.
         `transforms_is_device` says that a numpy array stands for device memory (the emulated build only).  `src_stream` (a
         hipStream_t as an int, or a torch stream) is the stream that writes device poses: the frame runs behind it, and it waits for
-        the kernel that reads them."""
+        the kernel that reads them.
+        `paints` makes it vello_hip_render_retained_painted, this frame's colours: what paint_array takes or a PAINT_DTYPE array (host
+        memory: copied during the call; None entries and PAINT_KEEP keep what the list was retained with), or paints in device
+        memory -- an int32 / uint32 tensor of n * 2 elements (flags, rgba) on the engine's GPU, or its address as an int -- which the
+        host never reads.  `paints_is_device` says that a numpy array stands for device memory (the emulated build only).
+        `src_stream` then orders device paints as it orders device poses."""
         numpy_is_device = bool(transforms_is_device)
         p = self._params(width, height, base_color, aa)
         ptr, stride = None, 0
@@ -521,10 +526,39 @@ class Engine:
             s, relay = _source_stream(src_stream)
         else:
             s = src_stream
-        r = self._lib.vello_hip_render_retained(self._h, tp, is_dev, ctypes.c_void_p(int(s)) if s else None, ctypes.byref(p), ptr, stride)
+        keep_p, pp, p_dev = None, None, 0
+        if paints is None:
+            pass
+        elif hasattr(paints, "data_ptr"):
+            import torch
+
+            if paints.dtype not in (torch.int32, torch.uint32) or not paints.is_contiguous():
+                raise ValueError("paints are a contiguous int32 / uint32 tensor of n * 2 elements (flags, rgba)")
+            if n is not None and paints.numel() != n * 2:
+                raise ValueError(f"{paints.numel()} words for {n} retained instances (2 each)")
+            if paints.is_cuda:
+                pp, p_dev = paints.data_ptr(), 1
+            else:
+                keep_p = paints.numpy()
+                pp = keep_p.ctypes.data
+        elif isinstance(paints, (int, np.integer)):
+            pp, p_dev = int(paints), 1
+        else:
+            if paints_is_device and not is_emulated(self._lib):
+                raise ValueError("a numpy array is host memory: device paints are a tensor on the GPU")
+            keep_p = paint_array(paints)
+            if n is not None and len(keep_p) != n:
+                raise ValueError(f"{len(keep_p)} paints for {n} retained instances")
+            # (an empty numpy array still has an address: n == 0 with a paint list is a call with a non-null pointer)
+            pp, p_dev = keep_p.ctypes.data, int(bool(paints_is_device))
+        stream_arg = ctypes.c_void_p(int(s)) if s else None
+        if paints is None:
+            r = self._lib.vello_hip_render_retained(self._h, tp, is_dev, stream_arg, ctypes.byref(p), ptr, stride)
+        else:
+            r = self._lib.vello_hip_render_retained_painted(self._h, tp, is_dev, pp, p_dev, stream_arg, ctypes.byref(p), ptr, stride)
         if relay is not None:
             relay[0].wait_stream(relay[1])
-        self._check(r, "render_retained")
+        self._check(r, "render_retained" if paints is None else "render_retained_painted")
 
     def release_retained(self):
         """vello_hip_release_retained: frees the retained list (fine when there is none)."""
