@@ -34,6 +34,7 @@
  *   vello_hip_render_retained_painted  ... and this frame's solid brushes  vello_encoding/src/encoding.rs:280-290
  *                              (encode_brush per appended scene)
  *   vello_hip_pick             (none upstream: the reference has no hit test; the contract is stated at the entry point)
+ *   vello_hip_pick_rect        (none upstream either: marquee selection; the contract is stated at the entry point)
  *   vello_hip_sync             queue.submit + device.poll                vello/src/wgpu_engine.rs:757
  *   vello_hip_set_frames_in_flight  back-to-back queue.submit without waiting  vello/src/wgpu_engine.rs:757
  *   vello_hip_get_bump         the robust path's bump download           vello/src/lib.rs:730, :753-761
@@ -559,14 +560,72 @@ typedef struct vello_hip_pick_hit { uint32_t draw_ix, instance_ix; } vello_hip_p
 int vello_hip_pick(vello_hip_ctx *ctx, const float *points /* n x 2 */, uint32_t n, int points_is_device,
                    void *src_stream /* nullable hipStream_t */, vello_hip_pick_hit *out /* n entries */, int out_is_device);
 /* Measurement seam: milliseconds between two events around the launches of the last vello_hip_pick -- every batch's zero fill and two
- * kernels, not the wait for the frame nor the copies of host points and results -- taken when vello_hip_set_profiling has any stage
- * enabled; 0 otherwise (scripts/pick_bench.py). */
+ * kernels, not the wait for the frame nor the copies of host points and results -- or of the last vello_hip_pick_rect (its zero fill
+ * and four kernels), whichever call came last; taken when vello_hip_set_profiling has any stage enabled; 0 otherwise
+ * (scripts/pick_bench.py, scripts/pick_rect_bench.py). */
 int vello_hip_pick_ms(vello_hip_ctx *ctx, float *ms_out);
 /* Test seam: the shapes of the pick's kernels, so that tests place their cases on the boundaries -- lines per workgroup of the line
  * pass, draw objects per step of the resolve pass, queries per batch under VELLO_HIP_DEBUG_PICK_SMALL_BATCHES, bytes of the
- * winding-table budget.  0 for any other `which`. */
-enum { VELLO_HIP_PICK_LINES_PER_WORKGROUP = 0, VELLO_HIP_PICK_DRAWS_PER_STEP = 1, VELLO_HIP_PICK_SMALL_BATCH = 2, VELLO_HIP_PICK_SCRATCH_BYTES = 3 };
+ * winding-table budget; lines per workgroup of vello_hip_pick_rect's line pass and draw objects per workgroup of its draw pass.  0 for
+ * any other `which`. */
+enum { VELLO_HIP_PICK_LINES_PER_WORKGROUP = 0, VELLO_HIP_PICK_DRAWS_PER_STEP = 1, VELLO_HIP_PICK_SMALL_BATCH = 2, VELLO_HIP_PICK_SCRATCH_BYTES = 3,
+       VELLO_HIP_PICK_RECT_LINES_PER_WORKGROUP = 4, VELLO_HIP_PICK_RECT_DRAWS_PER_WORKGROUP = 5 };
 uint32_t vello_hip_pick_constant(int which);
+
+/* Marquee selection: which draw objects, and which instances, a rectangle of the frame submitted last touches and which it encloses --
+ * "the frame" exactly as vello_hip_pick defines it.  The reference has no such query; like vello_hip_pick this extends the boundary
+ * and the contract is stated here.  It reads what the frame left on the device (the line soup in target space, the path boxes with
+ * their fill rules, the draw monoids, the composition's draw-tag prefix); the words it writes are what a caller turns into the paints
+ * of vello_hip_render_retained_painted, in device memory if it likes, so a selection can be shown in the next frame without the host
+ * reading it.  draws_out[i] is the word of draw object i, instances_out[k] the word of instance k of a frame composed from instances
+ * (vello_hip_render_instances, _painted, vello_hip_render_retained, _retained_painted); a word holds VELLO_HIP_REGION_TOUCHED,
+ * VELLO_HIP_REGION_ENCLOSED, both or neither, and no other bit.
+ *   0. THE REGION R'.  rect is (x0, y0, x1, y1) in target pixel coordinates, f32.  With W and H the frame's target size and all
+ *      arithmetic in f32: x0' = max(min(x0, x1), 0), x1' = min(max(x0, x1), W), and y0', y1' likewise with H -- a rectangle dragged
+ *      right to left is ordinary input, infinities clamp.  R' is EMPTY when a coordinate is NaN or !(x0' < x1' && y0' < y1'); an empty
+ *      R' selects nothing: every output word is 0, the counts are 0, the call returns VELLO_HIP_OK.  The probe point C of a non-empty
+ *      R': cx = x0' + (x1' - x0') * 0.5f, replaced by x0' when !(cx < x1'); cy likewise.  C lies in the target, and cy < H.
+ *   1. PER PATH, over the counted lines of the soup (path_ix < n_paths).  Every comparison is written so that a NaN coordinate fails.
+ *      MEETS: some line (p0, p1) of the path passes both (a) the f32 box test, all strict: min(p0x, p1x) < x1' && max(p0x, p1x) >
+ *      x0' && min(p0y, p1y) < y1' && max(p0y, p1y) > y0', and (b) the four corners of R' are not all strictly on one side of it: with
+ *      d(q) = (p1x - p0x) * (qy - p0y) - (qx - p0x) * (p1y - p0y), formed in f64 from the promoted f32 values without contraction (as
+ *      in vello_hip_pick's rule 1), the four d are not all > 0 and not all < 0.  (Together: the separating-axis test of a segment
+ *      against a box.  Strict, so a line that only runs along the boundary of R' does not meet it.)
+ *      HIT: the path is hit at C by vello_hip_pick's rule 1 -- the same winding sum and fill rule, without rule 3's in-target test.
+ *      TOUCH = MEETS or HIT: an outline crosses R', or R' lies inside the fill (a marquee within a large shape meets no line).
+ *      BOXED: the path's PathBbox (the integer box flatten leaves) satisfies x0' <= bx0 && bx1 <= x1' && y0' <= by0 && by1 <= y1'.
+ *   2. PER DRAW OBJECT, walking the draw objects with vello_hip_pick's clip stack: BeginClip pushes TOUCH of its path, a matched
+ *      EndClip pops; a paint draw (the pick's six tags) is TOUCHED when TOUCH holds for its own path and every bit on the stack is
+ *      set, and ENCLOSED when it is TOUCHED and its path is BOXED.  Every other draw object's word is 0.  THIS IS A PER-PATH RULE, NOT
+ *      A PER-PIXEL ONE: a draw can be TOUCHED although the part of it inside R' is covered by later draws, or although its clip meets
+ *      R' somewhere else than it does.  Blend modes and alpha play no part, as in a pick.
+ *   3. PER INSTANCE k, which owns the draws [prefix[k], prefix[k + 1]): TOUCHED when one of its draws is TOUCHED; ENCLOSED when one of
+ *      its draws is ENCLOSED and none of its paint draws whose path box is non-empty (bx0 < bx1 && by0 < by1) fails to be ENCLOSED.
+ *      Empty fragments get 0.
+ *   4. INDEPENDENT OF VIEWPORT CULLING (vello_hip_set_viewport_cull).  A culled line lies wholly at y <= 0, at y >= 16 * ceil(H / 16)
+ *      or at x >= 16 * ceil(W / 16): it fails a strict box test against R', which lies in [0, W] x [0, H], and a leftward ray from C
+ *      (0 <= cy < H, cx < W) cannot count it.  Path boxes do not change under culling (rule 1 of that contract).
+ *   5. COUNTS.  counts_out receives the four totals, in host memory, whenever the call succeeds.
+ *   6. SIZES AND REFUSALS.  vello_hip_pick_rect_sizes gives the frame's n_draw_objects and its instance count (0: the frame was not
+ *      composed from instances); the outputs that are not NULL have exactly these sizes.  VELLO_HIP_E_INVALID, with
+ *      vello_hip_last_error naming the rule, nothing enqueued and every output untouched: a NULL context or rect; draws_out,
+ *      instances_out and counts_out all NULL; draws_out with n_draws different from the frame's count; instances_out with n_instances
+ *      different from the frame's instance count, or on a frame that has no instances; a device output that is misaligned or (GPU
+ *      builds) not device memory of the context's device; no frame to answer against by vello_hip_pick's rules (never rendered, pools
+ *      grown since, scene replaced since).  A frame with bump.failed != 0 returns the code vello_hip_sync reports for it and writes
+ *      nothing, as vello_hip_pick does.
+ * One rectangle per call, in host memory.  THE CALL BLOCKS, on the frame's stream behind the frame, like vello_hip_pick; with
+ * out_is_device != 0 draws_out and instances_out are device memory (4-byte aligned) that the kernels write directly.  It does not
+ * move the rotation of the in-flight buffer sets, allocates no scene buffer and writes none of the frame's buffers: its scratch (two
+ * words per path, one per instance, one per workgroup of the draw pass) is the context's own.  Out of scope: lassos, several
+ * rectangles a call, rectangles in device memory, per-pixel visibility. */
+enum { VELLO_HIP_REGION_TOUCHED = 1, VELLO_HIP_REGION_ENCLOSED = 2 };
+typedef struct vello_hip_region_counts { uint32_t draws_touched, draws_enclosed, instances_touched, instances_enclosed; } vello_hip_region_counts;
+int vello_hip_pick_rect_sizes(vello_hip_ctx *ctx, uint32_t *n_draws_out, uint32_t *n_instances_out);
+int vello_hip_pick_rect(vello_hip_ctx *ctx, const float rect[4] /* x0 y0 x1 y1, host */,
+                        uint32_t *draws_out /* nullable */, uint32_t n_draws,
+                        uint32_t *instances_out /* nullable */, uint32_t n_instances,
+                        int out_is_device, vello_hip_region_counts *counts_out /* nullable, host */);
 /* Test seam: the sizes at which the pipeline's kernels and the host's launch switches cut their work, so that tests place tags, draw
  * objects, clips, lines and tile rows on those boundaries -- tags per partition of the pathtag scan's look-back and per block of
  * flatten's light pass; draw objects per partition of the draw scan; clips per partition of the clip kernels; draw objects (paths)

@@ -108,6 +108,19 @@ pub struct vello_hip_pick_hit {
     pub instance_ix: u32,
 }
 
+/// The four totals of one `vello_hip_pick_rect` call.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct vello_hip_region_counts {
+    pub draws_touched: u32,
+    pub draws_enclosed: u32,
+    pub instances_touched: u32,
+    pub instances_enclosed: u32,
+}
+
+/// The two bits of a word of `vello_hip_pick_rect`.
+pub const VELLO_HIP_REGION_TOUCHED: u32 = 1;
+pub const VELLO_HIP_REGION_ENCLOSED: u32 = 2;
 /// The header's `#define`s of the same names: no draw object / no instance, and the most points of one `vello_hip_pick` call (4096).
 pub const VELLO_HIP_PICK_NONE: u32 = 0xFFFF_FFFF;
 pub const VELLO_HIP_PICK_MAX_POINTS: u32 = 0x1000;
@@ -115,6 +128,8 @@ pub const VELLO_HIP_PICK_LINES_PER_WORKGROUP: c_int = 0;
 pub const VELLO_HIP_PICK_DRAWS_PER_STEP: c_int = 1;
 pub const VELLO_HIP_PICK_SMALL_BATCH: c_int = 2;
 pub const VELLO_HIP_PICK_SCRATCH_BYTES: c_int = 3;
+pub const VELLO_HIP_PICK_RECT_LINES_PER_WORKGROUP: c_int = 4;
+pub const VELLO_HIP_PICK_RECT_DRAWS_PER_WORKGROUP: c_int = 5;
 pub const VELLO_HIP_PAINT_KEEP: u32 = 0;
 pub const VELLO_HIP_PAINT_SOLID: u32 = 1;
 pub const VELLO_HIP_AA_AREA: u32 = 0;
@@ -158,6 +173,8 @@ unsafe extern "C" {
     pub fn vello_hip_pick(ctx: *mut vello_hip_ctx, points: *const f32, n: u32, points_is_device: c_int, src_stream: *mut c_void, out: *mut vello_hip_pick_hit, out_is_device: c_int) -> c_int;
     pub fn vello_hip_pick_ms(ctx: *mut vello_hip_ctx, ms_out: *mut f32) -> c_int;
     pub fn vello_hip_pick_constant(which: c_int) -> u32;
+    pub fn vello_hip_pick_rect_sizes(ctx: *mut vello_hip_ctx, n_draws_out: *mut u32, n_instances_out: *mut u32) -> c_int;
+    pub fn vello_hip_pick_rect(ctx: *mut vello_hip_ctx, rect: *const f32, draws_out: *mut u32, n_draws: u32, instances_out: *mut u32, n_instances: u32, out_is_device: c_int, counts_out: *mut vello_hip_region_counts) -> c_int;
     pub fn vello_hip_stage_constant(which: c_int) -> u32;
     pub fn vello_hip_resize_image_atlas(ctx: *mut vello_hip_ctx, width: u32, height: u32) -> c_int;
     pub fn vello_hip_write_image(ctx: *mut vello_hip_ctx, x: u32, y: u32, width: u32, height: u32, rgba8: *const u8, stride: usize) -> c_int;

@@ -11,11 +11,12 @@ from ._lib import load_library, library_path, VelloHipError
 from .kurbo import Affine, BezPath, Circle, Rect, RoundedRect, Line, Stroke, Join, Cap
 from .scene import (Scene, Fill, Color, BlendMode, Mix, Compose, Gradient, Extend, InterpolationAlphaSpace, ImageData, ImageBrush,
                     ImageFormat, ImageAlphaType, ImageQuality, Resolver, Resolved)
-from .renderer import Renderer, RenderParams, AaConfig, RendererOptions, Engine, Layout, FragmentLibrary, INSTANCE_DTYPE, PAINT_DTYPE, PICK_NONE, paint_array
+from .renderer import (Renderer, RenderParams, AaConfig, RendererOptions, Engine, Layout, FragmentLibrary, INSTANCE_DTYPE, PAINT_DTYPE, PICK_NONE, REGION_TOUCHED, REGION_ENCLOSED,
+                       paint_array)
 
 __all__ = [
     "load_library", "library_path", "VelloHipError", "Affine", "BezPath", "Circle", "Rect", "RoundedRect", "Line",
     "Stroke", "Join", "Cap", "Scene", "Fill", "Color", "BlendMode", "Mix", "Compose", "Renderer", "RenderParams",
     "AaConfig", "RendererOptions", "Engine", "Layout", "Gradient", "Extend", "InterpolationAlphaSpace", "ImageData", "ImageBrush",
-    "ImageFormat", "ImageAlphaType", "ImageQuality", "Resolver", "Resolved", "FragmentLibrary", "INSTANCE_DTYPE", "PAINT_DTYPE", "PICK_NONE", "paint_array",
+    "ImageFormat", "ImageAlphaType", "ImageQuality", "Resolver", "Resolved", "FragmentLibrary", "INSTANCE_DTYPE", "PAINT_DTYPE", "PICK_NONE", "REGION_TOUCHED", "REGION_ENCLOSED", "paint_array",
 ]

@@ -65,6 +65,13 @@ class PaintStruct(ctypes.Structure):  # vello_hip_paint
     _fields_ = [("flags", ctypes.c_uint32), ("rgba", ctypes.c_uint32)]
 
 
+class RegionCounts(ctypes.Structure):  # vello_hip_region_counts
+    _fields_ = [(n, ctypes.c_uint32) for n in ("draws_touched", "draws_enclosed", "instances_touched", "instances_enclosed")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 def load_library():
     """Loads the product library; raises (never falls back) when it is missing."""
     global _LIB
@@ -114,6 +121,8 @@ def load_library():
     sig("vello_hip_release_retained", i32, [vp])
     sig("vello_hip_pick", i32, [vp, vp, u32, i32, vp, vp, i32])
     sig("vello_hip_pick_constant", u32, [i32])
+    sig("vello_hip_pick_rect_sizes", i32, [vp, c.POINTER(u32), c.POINTER(u32)])
+    sig("vello_hip_pick_rect", i32, [vp, vp, vp, u32, vp, u32, i32, c.POINTER(RegionCounts)])
     sig("vello_hip_stage_constant", u32, [i32])
     sig("vello_hip_pick_ms", i32, [vp, c.POINTER(c.c_float)])
     sig("vello_hip_set_frames_in_flight", i32, [vp, u32])

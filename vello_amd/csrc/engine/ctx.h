@@ -208,7 +208,9 @@ struct vello_hip_ctx {
     vk::DevBuf copy_descs;  // vello_hip_copy_images_device: the batch's AtlasCopyDesc table (written and read on the upload stream only)
     // vello_hip_pick (blocking: idle between calls): a batch's winding table, host points on their way in, a host result on its way out
     vk::DevBuf pick_winding, pick_points, pick_out;
-    float pick_ms = 0.f;  // device time of the last pick's launches, taken while profiling is on (vello_hip_pick_ms)
+    float pick_ms = 0.f;  // device time of the last pick's (or pick_rect's) launches, taken while profiling is on (vello_hip_pick_ms)
+    // vello_hip_pick_rect (blocking too): RegionArgs::scratch, and host outputs on their way out ([n_draw] + [n_inst] words)
+    vk::DevBuf region_scratch, region_out;
     uint32_t debug_flags = 0;  // VELLO_HIP_DEBUG_*
     bool force_brushes = false;  // pre-warm: run fine's brush specialisation on a scene without brushes
     uint32_t last_render_attempts = 0;  // rounds the last vello_hip_render needed (robust mode)
@@ -266,6 +268,16 @@ void drop_retained(vello_hip_ctx *c);
 int acquire_staging(vello_hip_ctx *c, size_t bytes, Staging *&out);
 // seams.hip
 hipEvent_t get_event(vello_hip_ctx *c);
+// pick.hip: what the queries on the frame submitted last share (vello_hip_pick, vello_hip_pick_rect)
+struct QueryFrame {
+    Lane *lane;
+    const SceneSlot *scene;
+    const uint32_t *prefix;  // null: the frame was not composed from instances
+    uint32_t n_inst;
+};
+const char *not_device_memory(vello_hip_ctx *c, const void *p, size_t bytes);
+const char *query_frame(vello_hip_ctx *c, QueryFrame &q);
+int judge_frame(vello_hip_ctx *c, const char *who, Lane &l, Bump &bump);
 
 // One step of enter_frame that an entry point has nothing to add to.
 constexpr auto no_step = [](Lane &) { return 0; };

@@ -404,4 +404,57 @@ struct PickArgs {
 void launch_pick_lines(const PickArgs &a, hipStream_t s);    // (nothing to launch for an empty soup or a scene without paths)
 void launch_pick_resolve(const PickArgs &a, hipStream_t s);  // a workgroup per query of the batch
 
+// Marquee selection (vello_hip_pick_rect, pick_rect.hip): what its four kernels are handed by value.  The frame's buffers are read
+// only, as in PickArgs.  R' and C of the contract are computed on the host (region_of) and travel as arguments, so they are
+// wave-uniform.  `scratch` is the context's, zero-filled on the frame's stream ahead of the launches, region_scratch_words(...) words:
+//   [n_paths]   MEETS: 1 once a line of the path meets R'          (k_region_lines ORs, the draw kernels read)
+//   [n_paths]   the winding of the path at C, wrapping u32         (k_region_lines adds, the draw kernels read)
+//   [n_inst]    per instance: REGION_TOUCHED | REGION_ENCLOSED of any of its draws, REGION_NOT_ALL once a paint draw with a non-empty
+//               path box is not ENCLOSED                           (k_region_draws ORs, k_region_instances reads)
+//   [4]         vello_hip_region_counts
+//   [chunks]    the clip-stack sum of each REGION_DRAW_CHUNK draws  (k_region_draw_totals writes, k_region_draws reads)
+//   REGION_LINES_CHUNK  lines per workgroup of k_region_lines, a lane each;
+//   REGION_DRAW_CHUNK   draw objects per workgroup of k_region_draw_totals and k_region_draws, a lane each.
+constexpr uint32_t REGION_LINES_CHUNK = 256u, REGION_DRAW_CHUNK = 256u;
+constexpr uint32_t REGION_TOUCHED = 1u, REGION_ENCLOSED = 2u, REGION_NOT_ALL = 4u;
+struct Region {
+    float x0, y0, x1, y1;  // R'
+    float cx, cy;          // C
+};
+// rule 0 of the contract; false: R' is empty
+inline bool region_of(const float rect[4], uint32_t width, uint32_t height, Region &r) {
+    const float w = (float)width, h = (float)height;
+    for (int k = 0; k < 4; k++)
+        if (rect[k] != rect[k]) return false;
+    const float xa = rect[0] < rect[2] ? rect[0] : rect[2], xb = rect[0] < rect[2] ? rect[2] : rect[0];
+    const float ya = rect[1] < rect[3] ? rect[1] : rect[3], yb = rect[1] < rect[3] ? rect[3] : rect[1];
+    r.x0 = xa > 0.0f ? xa : 0.0f, r.x1 = xb < w ? xb : w;
+    r.y0 = ya > 0.0f ? ya : 0.0f, r.y1 = yb < h ? yb : h;
+    if (!(r.x0 < r.x1 && r.y0 < r.y1)) return false;
+    r.cx = r.x0 + (r.x1 - r.x0) * 0.5f;
+    if (!(r.cx < r.x1)) r.cx = r.x0;
+    r.cy = r.y0 + (r.y1 - r.y0) * 0.5f;
+    if (!(r.cy < r.y1)) r.cy = r.y0;
+    return true;
+}
+inline uint32_t region_draw_chunks(uint32_t n_draw) { return (uint32_t)(((uint64_t)n_draw + REGION_DRAW_CHUNK - 1u) / REGION_DRAW_CHUNK); }
+inline size_t region_scratch_words(uint32_t n_paths, uint32_t n_inst, uint32_t n_draw) {
+    return 2u * (size_t)n_paths + n_inst + 4u + region_draw_chunks(n_draw);
+}
+struct RegionArgs {
+    const LineSoup *lines;
+    const uint32_t *draw_tags;      // [n_draw]
+    const DrawMonoid *draw_monoids;
+    const PathBbox *path_bboxes;
+    const uint32_t *prefix;         // nullable: the frame was not composed from instances
+    uint32_t *scratch;              // the layout above
+    uint32_t *draws_out;            // nullable [n_draw]
+    uint32_t *instances_out;        // nullable [n_inst]
+    uint32_t n_lines, n_paths, n_draw, n_inst;
+    Region r;
+};
+void launch_region_lines(const RegionArgs &a, hipStream_t s);      // (nothing to launch for an empty soup or a scene without paths)
+void launch_region_draws(const RegionArgs &a, hipStream_t s);      // the two launches of the draw pass (none for a frame without draws)
+void launch_region_instances(const RegionArgs &a, hipStream_t s);  // (none for a frame without instances)
+
 }  // namespace vk

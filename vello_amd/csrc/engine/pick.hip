@@ -3,30 +3,14 @@
 // the frame left in its lane -- the line soup, the draw monoids, the path boxes' draw flags -- and write a scratch table and the
 // answers; nothing the frame path reads is written.
 #include "ctx.h"
+#include "pick_common.h"
 
 namespace vk {
 
 namespace {
 
-// A LineSoup record (24 B, 8-byte aligned) as three 8-byte loads, as k_path_count reads it (path.hip load_line).
-struct __attribute__((aligned(8))) PickWords2 { uint32_t a, b; };
-__device__ __forceinline__ LineSoup pick_load_line(const LineSoup *__restrict__ lines, uint32_t ix) {
-    const PickWords2 *p = reinterpret_cast<const PickWords2 *>(lines + ix);
-    const PickWords2 w0 = p[0], w1 = p[1], w2 = p[2];
-    LineSoup l;
-    l.path_ix = w0.a; l.pad = w0.b;
-    l.p0x = __uint_as_float(w1.a); l.p0y = __uint_as_float(w1.b);
-    l.p1x = __uint_as_float(w2.a); l.p1y = __uint_as_float(w2.b);
-    return l;
-}
-
 // rule 3: a point outside the target, a NaN (every comparison false) or an infinity misses
 __device__ __forceinline__ bool pick_in_target(float qx, float qy, float w, float h) { return qx >= 0.0f && qx < w && qy >= 0.0f && qy < h; }
-
-__device__ __forceinline__ bool pick_is_paint(uint32_t tag) {
-    return tag == DRAWTAG_FILL_COLOR || tag == DRAWTAG_FILL_LIN_GRADIENT || tag == DRAWTAG_FILL_RAD_GRADIENT || tag == DRAWTAG_FILL_SWEEP_GRADIENT ||
-           tag == DRAWTAG_FILL_IMAGE || tag == DRAWTAG_BLURRED_ROUNDED_RECT;
-}
 
 }  // namespace
 
@@ -143,7 +127,7 @@ using namespace vk;
 static_assert(PICK_NONE == VELLO_HIP_PICK_NONE && PICK_MAX_POINTS == VELLO_HIP_PICK_MAX_POINTS && sizeof(vello_hip_pick_hit) == 8,
               "k_pick_resolve writes vello_hip_pick_hit entries");
 
-namespace {
+namespace vk {
 
 // Why `bytes` bytes at `p` are not what a kernel of this context may be handed as device memory (nullptr: they are): the test
 // vello_hip_render_retained applies to device poses.  The emulated build has one address space and tests the alignment only.
@@ -165,7 +149,46 @@ const char *not_device_memory(vello_hip_ctx *c, const void *p, size_t bytes) {
     return nullptr;
 }
 
-}  // namespace
+// "The frame" of a query: the lane of the frame submitted last, its scene and -- a frame composed from instances -- the draw-tag
+// prefix: the lane's own table, or the retained list's copy.  nullptr, or why there is no frame to answer against.
+const char *query_frame(vello_hip_ctx *c, QueryFrame &q) {
+    Lane &l = c->lanes[c->last_lane];
+    if (!c->have_cfg || !l.used || !l.flatten_ran || !l.zero_region.ptr) return "no frame has been rendered";
+    const SceneSlot &sc = slot_of(c, l);
+    if (!sc.resident || l.frame_generation != sc.generation) return "the scene of the last frame has been replaced since";
+    q.lane = &l;
+    q.scene = &sc;
+    q.prefix = nullptr;
+    q.n_inst = 0u;
+    if (l.which == LaneScene::Own && l.own.composed && l.compose_n != 0u) {
+        q.prefix = (const uint32_t *)l.compose_table.ptr + 2u * ((size_t)l.compose_n + 1u);
+        q.n_inst = l.compose_n;
+    } else if (l.which == LaneScene::Retained && c->retained_n != 0u) {
+        q.prefix = (const uint32_t *)c->retained_prefix.ptr;
+        q.n_inst = c->retained_n;
+    }
+    return nullptr;
+}
+
+// Waits for the query's frame and judges it as vello_hip_sync does -- without that call's side effects.  `who` heads the message.
+int judge_frame(vello_hip_ctx *c, const char *who, Lane &l, Bump &bump) {
+    HIP_TRY(c, hipStreamSynchronize(l.stream));
+    HIP_TRY(c, hipMemcpy(&bump, l.zero_region.ptr, sizeof bump, hipMemcpyDeviceToHost));
+    if (bump.failed == 0u) return VELLO_HIP_OK;
+    const std::string head = std::string(who) + ": ";
+    if ((bump.failed & FAILED_SCENE) != 0u) {
+        c->last_error = head + "the frame was discarded (its path tag stream or its poses contradict its scene)";
+        return VELLO_HIP_E_INVALID;
+    }
+    if ((bump.failed & FAILED_INTERNAL) != 0u) {
+        c->last_error = head + "the frame was discarded (an engine-internal wait gave up)";
+        return VELLO_HIP_E_INTERNAL;
+    }
+    c->last_error = head + "the frame overflowed a pool (bump.failed=" + std::to_string(bump.failed) + "): its line soup is short";
+    return VELLO_HIP_E_CAPACITY;
+}
+
+}  // namespace vk
 
 extern "C" {
 
@@ -175,6 +198,8 @@ uint32_t vello_hip_pick_constant(int which) {
     case VELLO_HIP_PICK_DRAWS_PER_STEP: return PICK_DRAW_CHUNK;
     case VELLO_HIP_PICK_SMALL_BATCH: return PICK_BATCH_FORCED;
     case VELLO_HIP_PICK_SCRATCH_BYTES: return (uint32_t)PICK_SCRATCH_BYTES;
+    case VELLO_HIP_PICK_RECT_LINES_PER_WORKGROUP: return REGION_LINES_CHUNK;
+    case VELLO_HIP_PICK_RECT_DRAWS_PER_WORKGROUP: return REGION_DRAW_CHUNK;
     default: return 0u;
     }
 }
@@ -197,10 +222,10 @@ int vello_hip_pick(vello_hip_ctx *c, const float *points, uint32_t n, int points
     if (!out) return refuse("out is NULL");
     if (n > VELLO_HIP_PICK_MAX_POINTS) return refuse(std::to_string(n) + " points (at most VELLO_HIP_PICK_MAX_POINTS = " + std::to_string(VELLO_HIP_PICK_MAX_POINTS) + ")");
     if (src_stream && !points_is_device) return refuse("src_stream goes with points in device memory");
-    Lane &l = c->lanes[c->last_lane];
-    if (!c->have_cfg || !l.used || !l.flatten_ran || !l.zero_region.ptr) return refuse("no frame has been rendered");
-    const SceneSlot &sc = slot_of(c, l);
-    if (!sc.resident || l.frame_generation != sc.generation) return refuse("the scene of the last frame has been replaced since");
+    QueryFrame qf;
+    if (const char *why = query_frame(c, qf)) return refuse(why);
+    Lane &l = *qf.lane;
+    const SceneSlot &sc = *qf.scene;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)n * 8u;
     if (points_is_device)
@@ -208,23 +233,9 @@ int vello_hip_pick(vello_hip_ctx *c, const float *points, uint32_t n, int points
     if (out_is_device)
         if (const char *why = not_device_memory(c, out, bytes)) return refuse(std::string("the address of a device result ") + why);
 
-    // the frame: wait for it, and judge it as vello_hip_sync does -- without that call's side effects
     hipStream_t st = l.stream;
-    HIP_TRY(c, hipStreamSynchronize(st));
     Bump bump;
-    HIP_TRY(c, hipMemcpy(&bump, l.zero_region.ptr, sizeof bump, hipMemcpyDeviceToHost));
-    if (bump.failed != 0u) {
-        if ((bump.failed & FAILED_SCENE) != 0u) {
-            c->last_error = "pick: the frame was discarded (its path tag stream or its poses contradict its scene)";
-            return VELLO_HIP_E_INVALID;
-        }
-        if ((bump.failed & FAILED_INTERNAL) != 0u) {
-            c->last_error = "pick: the frame was discarded (an engine-internal wait gave up)";
-            return VELLO_HIP_E_INTERNAL;
-        }
-        c->last_error = "pick: the frame overflowed a pool (bump.failed=" + std::to_string(bump.failed) + "): its line soup is short";
-        return VELLO_HIP_E_CAPACITY;
-    }
+    if (int r = judge_frame(c, "pick", l, bump)) return r;
 
     const Config &cfg = l.frame_cfg;
     PickArgs a{};
@@ -237,14 +248,8 @@ int vello_hip_pick(vello_hip_ctx *c, const float *points, uint32_t n, int points
     a.path_bboxes = (const PathBbox *)l.buf[VELLO_HIP_BUF_PATH_BBOXES].ptr;
     a.width = cfg.target_width;
     a.height = cfg.target_height;
-    // the draw-tag prefix of a frame composed from instances: the lane's own table, or the retained list's copy
-    if (l.which == LaneScene::Own && l.own.composed && l.compose_n != 0u) {
-        a.prefix = (const uint32_t *)l.compose_table.ptr + 2u * ((size_t)l.compose_n + 1u);
-        a.n_inst = l.compose_n;
-    } else if (l.which == LaneScene::Retained && c->retained_n != 0u) {
-        a.prefix = (const uint32_t *)c->retained_prefix.ptr;
-        a.n_inst = c->retained_n;
-    }
+    a.prefix = qf.prefix;
+    a.n_inst = qf.n_inst;
 
     const uint32_t batch = pick_batch(a.n_paths, (c->debug_flags & VELLO_HIP_DEBUG_PICK_SMALL_BATCHES) != 0u);
     const size_t row_bytes = (size_t)a.n_paths * 4u;

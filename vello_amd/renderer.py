@@ -7,7 +7,7 @@ import enum
 import numpy as np
 
 from ._lib import (load_library, is_emulated, VelloHipError, Capacities, Bump, LayoutStruct, RenderParamsStruct, ImageCopyStruct, FragmentStruct,
-                   InstanceStruct, PaintStruct)
+                   InstanceStruct, PaintStruct, RegionCounts)
 from .scene import Color, ImageAlphaType, ImageData, ImageFormat
 
 
@@ -30,6 +30,7 @@ BUFFERS = ["scene", "config", "tag_monoids", "path_bboxes", "bump", "lines", "dr
 E_CAPACITY = -4
 PICK_NONE = 0xFFFFFFFF  # VELLO_HIP_PICK_NONE: no draw object under the point / the frame was not composed from instances
 PICK_MAX_POINTS = 4096  # VELLO_HIP_PICK_MAX_POINTS
+REGION_TOUCHED, REGION_ENCLOSED = 1, 2  # VELLO_HIP_REGION_*: the two bits of a word of Engine.pick_rect
 
 
 class RenderParams:
@@ -619,15 +620,68 @@ class Engine:
         return out
 
     def pick_ms(self):
-        """vello_hip_pick_ms: device milliseconds of the last pick's launches, taken while set_profiling has any stage enabled."""
+        """vello_hip_pick_ms: device milliseconds of the last pick's (or pick_rect's) launches, taken while set_profiling has any stage enabled."""
         ms = ctypes.c_float()
         self._check(self._lib.vello_hip_pick_ms(self._h, ctypes.byref(ms)), "pick_ms")
         return float(ms.value)
 
+    def pick_rect_sizes(self):
+        """vello_hip_pick_rect_sizes: (draw objects, instances) of the frame submitted last -- the sizes of pick_rect's two outputs;
+        0 instances when the frame was not composed from instances."""
+        nd, ni = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._lib.vello_hip_pick_rect_sizes(self._h, ctypes.byref(nd), ctypes.byref(ni)), "pick_rect_sizes")
+        return int(nd.value), int(ni.value)
+
+    def pick_rect(self, rect, draws_out=None, instances_out=None, draws=True, instances=True, out_is_device=None):
+        """vello_hip_pick_rect: marquee selection on the frame submitted last (the contract is in include/vello_hip.h).  `rect` is
+        (x0, y0, x1, y1) in target pixels.  Returns (draws, instances, counts): a uint32 word per draw object and per instance --
+        REGION_TOUCHED, REGION_ENCLOSED, both or 0 -- and the four totals as a dict.  Without `draws_out` / `instances_out` the words
+        come back in new numpy arrays; `draws=False` / `instances=False` leave an output out (None is returned for it), and
+        `instances` is None as well for a frame that was not composed from instances.  `draws_out` / `instances_out`: C-contiguous
+        uint32 numpy arrays of pick_rect_sizes() entries (host memory), or int32 / uint32 tensors on the GPU, which the kernels write
+        in place -- both of one kind; they are returned.  `out_is_device` says that numpy arrays stand for device memory (the emulated
+        build only).  Blocks.  A frame that failed raises VelloHipError with the code vello_hip_sync reports for it in `.code`."""
+        r4 = np.ascontiguousarray(rect, dtype=np.float32).reshape(-1)
+        if r4.size != 4:
+            raise ValueError("rect is (x0, y0, x1, y1)")
+        n_draw, n_inst = self.pick_rect_sizes()
+        if draws_out is None and draws:
+            if out_is_device:
+                raise ValueError("out_is_device goes with draws_out / instances_out")
+            draws_out = np.zeros(n_draw, dtype=np.uint32)
+        if instances_out is None and instances and n_inst:
+            if out_is_device:
+                raise ValueError("out_is_device goes with draws_out / instances_out")
+            instances_out = np.zeros(n_inst, dtype=np.uint32)
+        kinds, ptrs = set(), []
+        for name, o in (("draws_out", draws_out), ("instances_out", instances_out)):
+            if o is None:
+                ptrs.append((None, 0))
+            elif isinstance(o, np.ndarray):
+                if o.dtype != np.uint32 or not o.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"{name} must be a C-contiguous uint32 array")
+                if out_is_device and not is_emulated(self._lib):
+                    raise ValueError("a numpy array is host memory: a device output is a tensor on the GPU")
+                kinds.add(bool(out_is_device))
+                ptrs.append((o.ctypes.data, o.size))
+            else:
+                if str(o.dtype) not in ("torch.int32", "torch.uint32") or not o.is_contiguous() or not o.is_cuda:
+                    raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor on the GPU (or a numpy array)")
+                kinds.add(True)
+                ptrs.append((o.data_ptr(), o.numel()))
+        if len(kinds) > 1:
+            raise ValueError("draws_out and instances_out are both host memory or both device memory")
+        counts = RegionCounts()
+        r = self._lib.vello_hip_pick_rect(self._h, r4.ctypes.data, ptrs[0][0], ptrs[0][1], ptrs[1][0], ptrs[1][1], int(bool(kinds and kinds.pop())),
+                                          ctypes.byref(counts))
+        self._check(r, "pick_rect")
+        return draws_out, instances_out, counts.as_dict()
+
     def pick_constants(self):
         """vello_hip_pick_constant: the shapes of the pick's kernels (a test seam) -- lines per workgroup of the line pass, draw objects
-        per step of the resolve pass, queries per batch under the pick_small_batches debug flag, bytes of the winding-table budget."""
-        names = ("lines_per_workgroup", "draws_per_step", "small_batch", "scratch_bytes")
+        per step of the resolve pass, queries per batch under the pick_small_batches debug flag, bytes of the winding-table budget;
+        lines per workgroup of pick_rect's line pass and draw objects per workgroup of its draw pass."""
+        names = ("lines_per_workgroup", "draws_per_step", "small_batch", "scratch_bytes", "rect_lines_per_workgroup", "rect_draws_per_workgroup")
         return {k: int(self._lib.vello_hip_pick_constant(i)) for i, k in enumerate(names)}
 
     STAGE_CONSTANTS = ("pathtag_part_tags", "flatten_block_tags", "draw_part", "clip_part", "draw_workgroup", "coarse_batch", "coarse_grid_bins",
