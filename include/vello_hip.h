@@ -256,6 +256,16 @@ uint64_t vello_hip_fused_launches(vello_hip_ctx *ctx);
  * vello_hip_render_frame's lanes): lets a test see that frames whose scenes fit the buffers they have allocate nothing -- a
  * re-allocation frees device memory, which waits for every frame in flight. */
 uint64_t vello_hip_scene_allocations(vello_hip_ctx *ctx);
+/* Scene indexes built since the context was created.  vello_hip_upload_scene (and vello_hip_upload_fragments through it) builds one
+ * for a scene too large for the small-scene launches (VELLO_HIP_SHAPE_FRONT_MAX_TAGS / _FRONT_MAX_DRAW_OBJECTS): the pathtag scan's
+ * output and verdict, the path boxes as the scan leaves them, and the scene's segment tags sorted into fills, stroked curves and
+ * stroked lines -- everything a frame of the resident scene would otherwise compute again from the same bytes, none of it a function
+ * of a transform.  Frames of vello_hip_render_resident read it in place of the scan and of the sorting half of flatten's light
+ * pass; every buffer a stage leaves is what it leaves without the index (tag monoids and path boxes bit for bit, the line soup as a
+ * multiset), and VELLO_HIP_BUF_TAG_MONOIDS shows the index's array.  The next upload drops it; so does a vello_hip_write_buffer to
+ * VELLO_HIP_BUF_SCENE of the resident scene, after which frames take the per-frame path until the next upload.  Private scenes
+ * (vello_hip_render_frame), composed frames and the retained list are not indexed.  Lets a test see that frames build none. */
+uint64_t vello_hip_scene_index_builds(vello_hip_ctx *ctx);
 int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                                   const vello_hip_render_params *params, vello_hip_capacities *out);
 
@@ -659,10 +669,13 @@ uint32_t vello_hip_stage_constant(int which);
  * VELLO_HIP_DEBUG_NO_FUSION launches every stage of a small scene as a kernel of its own (normally the workgroups of consecutive
  * stages up to tile_alloc share launches when the scene is small enough for launch boundaries to matter): same buffers.
  * VELLO_HIP_DEBUG_PICK_SMALL_BATCHES answers the queries of a vello_hip_pick call three at a time (normally as many as fit the
- * winding-table budget): same answers -- so that a handful of queries on a small scene spans several batches. */
+ * winding-table budget): same answers -- so that a handful of queries on a small scene spans several batches.
+ * VELLO_HIP_DEBUG_NO_SCENE_INDEX renders a resident scene that has an index (vello_hip_scene_index_builds) without it: the zero
+ * fill, the pathtag scan and the whole-stream light pass of every frame, as for a scene that has none: same buffers -- for A/Bs and so
+ * that tests can hold the two paths to each other.  It applies to whole frames: set it between frames, not between the stages of one. */
 enum { VELLO_HIP_DEBUG_NO_CULL = 1, VELLO_HIP_DEBUG_STROKE_KERNEL = 2, VELLO_HIP_DEBUG_SEQ_CLIP = 4, VELLO_HIP_DEBUG_FINE_SLICES = 8,
        VELLO_HIP_DEBUG_FLATTEN_COOP = 16, VELLO_HIP_DEBUG_FLATTEN_ALONE = 32, VELLO_HIP_DEBUG_NO_FUSION = 64,
-       VELLO_HIP_DEBUG_PICK_SMALL_BATCHES = 128,
+       VELLO_HIP_DEBUG_PICK_SMALL_BATCHES = 128, VELLO_HIP_DEBUG_NO_SCENE_INDEX = 256,
        /* measurement seam: bits 24-27 = 1 + the last stage vello_hip_render_resident launches (0: all of them) -- what the stages
         * up to k cost with frames in flight (scripts/experiments/r6_stage_marginal.py); the frames are incomplete */
        VELLO_HIP_DEBUG_LAST_STAGE_SHIFT = 24 };

@@ -153,6 +153,7 @@ pub const VELLO_HIP_DEBUG_FLATTEN_COOP: u32 = 16;
 pub const VELLO_HIP_DEBUG_FLATTEN_ALONE: u32 = 32;
 pub const VELLO_HIP_DEBUG_NO_FUSION: u32 = 64;
 pub const VELLO_HIP_DEBUG_PICK_SMALL_BATCHES: u32 = 128;
+pub const VELLO_HIP_DEBUG_NO_SCENE_INDEX: u32 = 256;
 pub const VELLO_HIP_STAGE_COUNT: usize = 11;
 
 unsafe extern "C" {
@@ -187,6 +188,7 @@ unsafe extern "C" {
     pub fn vello_hip_set_auto_grow(ctx: *mut vello_hip_ctx, enabled: c_int) -> c_int;
     pub fn vello_hip_set_viewport_cull(ctx: *mut vello_hip_ctx, enabled: c_int) -> c_int;
     pub fn vello_hip_scene_allocations(ctx: *mut vello_hip_ctx) -> u64;
+    pub fn vello_hip_scene_index_builds(ctx: *mut vello_hip_ctx) -> u64;
     pub fn vello_hip_set_view_transform(ctx: *mut vello_hip_ctx, view: *const f32) -> c_int;
     pub fn vello_hip_estimate_capacities_view(scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, params: *const vello_hip_render_params, view: *const f32, out: *mut vello_hip_capacities) -> c_int;
     pub fn vello_hip_set_debug_flags(ctx: *mut vello_hip_ctx, flags: u32) -> c_int;

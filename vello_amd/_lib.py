@@ -138,6 +138,7 @@ def load_library():
     sig("vello_hip_last_render_attempts", u32, [vp])
     sig("vello_hip_fused_launches", ctypes.c_uint64, [vp])
     sig("vello_hip_scene_allocations", ctypes.c_uint64, [vp])
+    sig("vello_hip_scene_index_builds", ctypes.c_uint64, [vp])
     sig("vello_hip_estimate_capacities", i32, [vp, sz, c.POINTER(LayoutStruct), c.POINTER(RenderParamsStruct), c.POINTER(Capacities)])
     sig("vello_hip_estimate_capacities_view", i32, [vp, sz, c.POINTER(LayoutStruct), c.POINTER(RenderParamsStruct), c.POINTER(c.c_float),
                                                c.POINTER(Capacities)])

@@ -28,6 +28,17 @@ inline uint32_t align_up(uint32_t len, uint32_t alignment) { return len + ((0u -
 // ramps and mask LUTs are shared read-only.  wgpu queues recordings without waiting (wgpu_engine.rs:757); here
 // consecutive frames additionally overlap on the GPU (coarse launches only one workgroup per bin, fine and
 // flatten are latency-bound, so a second frame fills the idle CUs): vello_hip_set_frames_in_flight.
+// What every frame of a resident scene would compute again from the same bytes: built once by
+// vello_hip_upload_scene for the shared slot, for scenes too large for k_front.  Nothing in it depends on a transform.
+struct SceneIndex {
+    DevBuf monoids;  // [n_tag_words + 4] the pathtag scan's output: every lane's Frame::tag_monoids
+    DevBuf bboxes;   // [n_paths + 1] the cleared boxes with the draw_flags / trans_ix the scan stores at the PATH markers
+    DevBuf lists;    // [3][n_tags] fill segment tags | stroked tags that are not lines | stroked lines (Frame::index_lists)
+    DevBuf counts;   // [4] the lists' lengths as the build kernel counted them
+    uint32_t n_fill = 0, n_strokes = 0, n_lines = 0;
+    uint32_t failed = 0;  // the scan's verdict: 0 or FAILED_SCENE
+    bool valid = false;   // dropped by the next upload into the slot and by a vello_hip_write_buffer to its scene
+};
 // A packed scene made resident: the bytes, the ramp texture and everything the host derives from the Layout.
 struct SceneSlot {
     DevBuf scene, ramps;
@@ -47,6 +58,7 @@ struct SceneSlot {
     // markers of open subpaths), stroked lines (-1: not known yet): picks the kernels that take the list (Frame::flatten_coop)
     int64_t heavy_curves = -1, heavy_strokes = -1;
     uint64_t generation = 0;  // bumped by every upload into the slot: a lane's finished frame speaks for the scene it rendered only
+    SceneIndex index;         // the shared slot only
     // The composed transform words of frames with a view (vello_hip_set_view_transform, Frame::xf_base): `view_sets` copies of
     // (n_xf + 1) * 6 words each, from word `view_at` of the scene's allocation -- behind the scene's bytes and their slack, never
     // part of what VELLO_HIP_BUF_SCENE shows.  The shared slot holds a copy per lane (frames in flight have views of their own), a
@@ -134,6 +146,7 @@ struct Lane {
     bool slices_on = false;   // the lane's latest frame ran with fine's slices enabled (an MSAA frame)
     uint32_t slice_cap_coarse = 0;  // slice blocks the lane's latest COARSE launch was told of (a later FINE must launch as many)
     uint32_t slice_fills_coarse = 0;  // ... and the slice size it cut with (0: no slices -- an area-AA frame)
+    bool frame_indexed = false;  // the lane's latest frame read the shared slot's index (VELLO_HIP_BUF_TAG_MONOIDS shows its array)
     bool flatten_ran = false;  // the control block holds flatten's counts (a partial vello_hip_run_stages range may stop before it)
     uint64_t frame_generation = 0;  // slot_of(...).generation when the lane's latest frame was set up
     uint64_t atlas_epoch_seen = 0;  // ctx::atlas_epoch the lane's stream has been ordered behind
@@ -216,6 +229,7 @@ struct vello_hip_ctx {
     uint32_t last_render_attempts = 0;  // rounds the last vello_hip_render needed (robust mode)
     uint64_t fused_launches = 0;  // k_front launches so far (vello_hip_fused_launches)
     uint64_t scene_allocations = 0;  // scene buffers allocated so far (vello_hip_scene_allocations)
+    uint64_t scene_index_builds = 0;  // scene indexes built so far (vello_hip_scene_index_builds)
     // last frame
     vk::Config cfg{};
     bool have_cfg = false;

@@ -223,6 +223,14 @@ struct Frame {
     const uint32_t *mask_lut8;
     const uint32_t *mask_lut16;
     uint32_t zero_bytes;     // the lane's zero region: Control + both look-back states (k_front clears it itself)
+    // A frame of an indexed scene (SceneIndex, ctx.h): tag_monoids is the index's array, the frame begins with k_frame_begin in the
+    // place of the zero fill and the pathtag scan, the light pass walks the index's fill list and the stroke workgroups and the
+    // heavy code read sections 1 and 2 from the index (index_lists laid out as heavy_list is: section s from word s * n_tags).
+    bool indexed;
+    const PathBbox *index_bboxes;  // [n_paths] the cleared boxes with the draw_flags / trans_ix the scan stores
+    const uint32_t *index_lists;   // [3][n_tags]: fill segment tags | stroked tags that are not lines | stroked lines
+    uint32_t index_n_fill, index_n_strokes, index_n_lines;
+    uint32_t index_failed;         // the scan's verdict: 0 or FAILED_SCENE
     uint32_t *front_sync;    // k_front's grid-barrier counter (per lane; only ever grows)
     Bump *bump() const { return &control->bump; }
 };
@@ -277,6 +285,12 @@ struct InstancePaintArgs {
 void launch_instance_paints(const Frame &f, bool check_paints, hipStream_t s);
 
 void launch_pathtag_scan(const Frame &f, hipStream_t s);
+// k_frame_begin (scan.hip), an indexed frame's first launch: the zero fill of the lane's zero region, the path boxes from the
+// index's template, control->heavy_count[1] / [2] and bump.failed from the index
+void launch_frame_begin(const Frame &f, hipStream_t s);
+// k_scene_index_lists (flatten.hip), once per upload: sorts the segment tags of a scanned scene (f.tag_monoids, f.control hold the
+// scan's output and verdict) into `lists` ([3][n_tags], Frame::index_lists) and counts them in counts[0 .. 2] (zeroed by the caller)
+void launch_scene_index_lists(const Frame &f, uint32_t *lists, uint32_t *counts, hipStream_t s);
 // (mid: when not null, an event is recorded behind every kernel of the stage but the last: per-KERNEL times of a stage of
 // several kernels, vello_hip_get_kernel_ms)
 // with_draw_scan: the draw stage's workgroups ride in k_flatten_light's launch (the caller then leaves launch_draw_scan out)

@@ -1112,22 +1112,24 @@ __device__ __forceinline__ void wave_bbox_update(PathBbox *path_bboxes, uint32_t
 // homogeneous (a wave mixing 8 cubics with 56 stroked lines runs the subdivision loop at 1/8 lane use).
 // Returns 0 = done, HEAVY_CURVE or HEAVY_STROKE.
 constexpr uint32_t HEAVY_CURVE = 1u, HEAVY_STROKE = 2u, HEAVY_STROKE_LINE = 3u;
-__device__ __forceinline__ uint32_t flatten_tag_light(Emitter &em, const Config &cfg, const uint32_t *scene, const TagMonoid *tag_monoids,
-                                                  PathBbox *path_bboxes, uint32_t ix, uint32_t &path_ix_out) {
-    PathTagData tag = compute_tag_monoid(cfg, scene, tag_monoids, ix);
-    uint32_t seg_type = tag.tag_byte & PATH_TAG_SEG_TYPE;
-    uint32_t path_ix = tag.monoid.path_ix;
-    path_ix_out = path_ix;
-    em.bx0 = 1e31f; em.by0 = 1e31f; em.bx1 = -1e31f; em.by1 = -1e31f;
+// The sorting half of the light pass: what kind of work a tag is.  A function of the tag byte and its style flags alone -- never of a
+// transform -- which is why k_scene_index_lists can do it once per upload (SceneIndex, ctx.h).  0: no segment (a marker), HEAVY_STROKE
+// / HEAVY_STROKE_LINE: a stroked tag, TAG_FILL_SEGMENT: the light pass's own.
+constexpr uint32_t TAG_FILL_SEGMENT = 4u;
+__device__ __forceinline__ uint32_t classify_tag(const Config &cfg, const uint32_t *scene, const PathTagData &tag) {
+    const uint32_t seg_type = tag.tag_byte & PATH_TAG_SEG_TYPE;
     // (a PATH marker's draw flags / transform index, flatten.wgsl:813-817: stored by k_pathtag_scan, scan.hip)
     if (seg_type == 0u) return 0u;
-    uint32_t style_ix = tag.monoid.style_ix;
-    uint32_t trans_ix = tag.monoid.trans_ix;
-    uint32_t style_flags = scene[(uint32_t)(cfg.layout.style_base + style_ix)];
+    const uint32_t style_flags = scene[(uint32_t)(cfg.layout.style_base + tag.monoid.style_ix)];
     // joins, caps, offset curves; stroked LINES (most of a map) are listed apart: they need no Euler spirals
     if ((style_flags & STYLE_FLAGS_STYLE) != 0u) return seg_type == PATH_TAG_LINETO ? HEAVY_STROKE_LINE : HEAVY_STROKE;
+    return TAG_FILL_SEGMENT;
+}
+// The per-frame half: a fill's segment under the frame's transform.  Returns 0 = done or HEAVY_CURVE.
+__device__ __forceinline__ uint32_t flatten_fill_segment(Emitter &em, const Config &cfg, const uint32_t *scene, const PathTagData &tag) {
+    const uint32_t path_ix = tag.monoid.path_ix;
     const uint32_t *pd = scene + cfg.layout.path_data_base;
-    Xform transform = read_transform(scene, cfg.layout.transform_base, trans_ix);
+    Xform transform = read_transform(scene, cfg.layout.transform_base, tag.monoid.trans_ix);
     CubicPoints pts = read_path_segment(pd, tag, false);
     // flatten_euler with offset == 0 (flatten.wgsl:340-352): points to device space, degenerate cubics emit nothing
     vec2 p0 = xf_apply(transform, pts.p0), p1 = xf_apply(transform, pts.p1), p2 = xf_apply(transform, pts.p2),
@@ -1138,6 +1140,15 @@ __device__ __forceinline__ uint32_t flatten_tag_light(Emitter &em, const Config 
     uint32_t line_ix = em.alloc(1u);
     em.write_xf(line_ix, path_ix, p0, p3, identity);  // the reference applies the (identity) transform here too
     return 0u;
+}
+__device__ __forceinline__ uint32_t flatten_tag_light(Emitter &em, const Config &cfg, const uint32_t *scene, const TagMonoid *tag_monoids,
+                                                  PathBbox *path_bboxes, uint32_t ix, uint32_t &path_ix_out) {
+    PathTagData tag = compute_tag_monoid(cfg, scene, tag_monoids, ix);
+    path_ix_out = tag.monoid.path_ix;
+    em.bx0 = 1e31f; em.by0 = 1e31f; em.bx1 = -1e31f; em.by1 = -1e31f;
+    const uint32_t kind = classify_tag(cfg, scene, tag);
+    if (kind != TAG_FILL_SEGMENT) return kind;
+    return flatten_fill_segment(em, cfg, scene, tag);
 }
 
 // (one workgroup of flatten's light pass: FLATTEN_BLOCK_TAGS tags from tag `block` x FLATTEN_BLOCK_TAGS on)
@@ -1418,10 +1429,11 @@ __device__ uint32_t g_stroke_tl_n;
 template <bool CULL, uint32_t CAP>
 __device__ __forceinline__ void stroke_workgroup(FlattenShared<CAP> &sh, ArcQueue &arcs, uint32_t block, uint32_t n_blocks, const Config &cfg,
                                  uint32_t n_tags, const uint32_t *__restrict__ scene, const TagMonoid *__restrict__ tag_monoids,
-                                 PathBbox *path_bboxes, Control *control, LineSoup *lines, uint32_t *heavy_list, uint32_t min_lines,
-                                 uint32_t *arc_items, uint32_t arc_shard_cap) {
+                                 PathBbox *path_bboxes, Control *control, LineSoup *lines, uint32_t *heavy_list, const uint32_t *__restrict__ stroke_lists,
+                                 uint32_t min_lines, uint32_t *arc_items, uint32_t arc_shard_cap) {
     const uint32_t tid = threadIdx.x;
-    const uint32_t n_lines_q = control->heavy_count[2];  // final: written by k_flatten_light
+    // (stroke_lists: what holds sections 1 and 2 -- the frame's heavy_list, or the scene index's lists, which no frame writes)
+    const uint32_t n_lines_q = control->heavy_count[2];  // final: written by k_flatten_light, or by k_frame_begin from the scene index
     if (n_lines_q < min_lines) return;  // the heavy workgroups take them
     if (block * 256u >= n_lines_q || (control->bump.failed & FAILED_SCENE) != 0u) return;
     if (tid == 0u) {
@@ -1438,7 +1450,7 @@ __device__ __forceinline__ void stroke_workgroup(FlattenShared<CAP> &sh, ArcQueu
     // 7.1 us): the list entries are requested TWO rounds ahead, the tag words and monoids ONE, from clamped addresses (a load under a
     // branch would wait for everything in flight: DESIGN.md 3.1), so a round starts with its data's addresses in registers.
     const uint32_t stride = n_blocks * 256u, last = n_lines_q - 1u;
-    const uint32_t *const list = heavy_list + 2u * (size_t)n_tags;
+    const uint32_t *const list = stroke_lists + 2u * (size_t)n_tags;
     uint32_t tag_ix_cur = list[minu(block * 256u + tid, last)];
     uint32_t tag_ix_next = list[minu(block * 256u + tid + stride, last)];
     uint32_t word_cur = scene[cfg.layout.path_tag_base + (tag_ix_cur >> 2)];
@@ -1555,7 +1567,7 @@ constexpr uint32_t HEAVY_FIRST = 1u, HEAVY_SET_ASIDE = 2u;
 template <uint32_t LISTS, bool COOP, bool CULL>
 __device__ __forceinline__ void heavy_workgroups(FlattenShared<FLATTEN_LDS_LINES> &sh, EulerCoopLds *coop, uint32_t block, uint32_t n_blocks, const Config &cfg, uint32_t n_tags,
                                                  const uint32_t *__restrict__ scene, const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
-                                                 Control *control, LineSoup *lines, const uint32_t *__restrict__ heavy_list,
+                                                 Control *control, LineSoup *lines, const uint32_t *__restrict__ heavy_list, const uint32_t *__restrict__ stroke_lists,
                                                  uint32_t stroke_kernel_min_lines, const uint32_t *__restrict__ arc_items, uint32_t arc_shard_cap) {
     constexpr bool FIRST = (LISTS & HEAVY_FIRST) != 0u, ASIDE = (LISTS & HEAVY_SET_ASIDE) != 0u;
     const uint32_t tid = threadIdx.x;
@@ -1627,9 +1639,9 @@ __device__ __forceinline__ void heavy_workgroups(FlattenShared<FLATTEN_LDS_LINES
         if (has_tag) {
             const uint32_t e1 = e - n_curves, e3 = e1 - n_strokes, e2 = e3 - n_handed;
             tag_ix = e < n_curves     ? heavy_list[e]
-                     : e1 < n_strokes ? heavy_list[n_tags + e1]
+                     : e1 < n_strokes ? stroke_lists[n_tags + e1]
                      : e3 < n_handed  ? heavy_list[3u * n_tags + e3]
-                                      : heavy_list[2u * n_tags + e2];
+                                      : stroke_lists[2u * n_tags + e2];
         }
         // (COOP is the host's choice for the scene, prepare_frame in frames.hip, Frame::flatten_coop: the kernels of the cooperative walk, with the fp64
         // routines out of line, or round 4's, every lane on its own with the routines inline -- flatten_walk.inc's head says why)
@@ -1672,7 +1684,7 @@ __device__ __forceinline__ void heavy_workgroups(FlattenShared<FLATTEN_LDS_LINES
 template <bool COOP, bool CULL>
 __global__ void __launch_bounds__(256, 2) k_flatten_main(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
                                                          const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
-                                                         Control *control, LineSoup *lines, uint32_t *heavy_list,
+                                                         Control *control, LineSoup *lines, uint32_t *heavy_list, const uint32_t *__restrict__ stroke_lists,
                                                          uint32_t stroke_kernel_min_lines, uint32_t *arc_items, uint32_t arc_shard_cap,
                                                          uint32_t n_heavy_blocks) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[FLATTEN_MAIN_LDS];
@@ -1680,11 +1692,11 @@ __global__ void __launch_bounds__(256, 2) k_flatten_main(Config cfg, uint32_t n_
         // (the heavy workgroups keep their four waves' EulerCoopLds where the stroke workgroups keep their arc queue)
         heavy_workgroups<HEAVY_FIRST, COOP, CULL>(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem), reinterpret_cast<EulerCoopLds *>(smem + FLATTEN_ARCS_AT),
                                       blockIdx.x, n_heavy_blocks, cfg, n_tags, scene, tag_monoids,
-                                      path_bboxes, control, lines, heavy_list, stroke_kernel_min_lines, arc_items, arc_shard_cap);
+                                      path_bboxes, control, lines, heavy_list, stroke_lists, stroke_kernel_min_lines, arc_items, arc_shard_cap);
     } else {
         stroke_workgroup<CULL>(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem), *reinterpret_cast<ArcQueue *>(smem + FLATTEN_ARCS_AT),
                          blockIdx.x - n_heavy_blocks, gridDim.x - n_heavy_blocks, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines,
-                         heavy_list, stroke_kernel_min_lines, arc_items, arc_shard_cap);
+                         heavy_list, stroke_lists, stroke_kernel_min_lines, arc_items, arc_shard_cap);
     }
 }
 
@@ -1695,7 +1707,7 @@ __global__ void __launch_bounds__(256, 2) k_flatten_tail(Config cfg, uint32_t n_
                                                          const uint32_t *__restrict__ arc_items, uint32_t arc_shard_cap) {
     __shared__ FlattenShared<FLATTEN_LDS_LINES> sh;
     // (what the stroke workgroups set aside -- arcs, and lines that were not straight after all: every lane on its own)
-    heavy_workgroups<HEAVY_SET_ASIDE, false, CULL>(sh, nullptr, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, 0u, arc_items,
+    heavy_workgroups<HEAVY_SET_ASIDE, false, CULL>(sh, nullptr, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, heavy_list, 0u, arc_items,
                                       arc_shard_cap);
 }
 
@@ -1706,24 +1718,192 @@ __global__ void __launch_bounds__(256, 2) k_flatten_tail(Config cfg, uint32_t n_
 template <bool CULL>
 __global__ void __launch_bounds__(256) k_flatten_strokes(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
                                                         const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes, Control *control,
-                                                        LineSoup *lines, uint32_t *heavy_list, uint32_t min_lines, uint32_t *arc_items,
-                                                        uint32_t arc_shard_cap) {
+                                                        LineSoup *lines, uint32_t *heavy_list, const uint32_t *__restrict__ stroke_lists, uint32_t min_lines,
+                                                        uint32_t *arc_items, uint32_t arc_shard_cap) {
     __shared__ FlattenShared<FLATTEN_STROKE_ROUND_LINES> sh;  // 30 KB of staging + 16 KB of arcs: three workgroups per CU
     __shared__ ArcQueue arcs;
-    stroke_workgroup<CULL>(sh, arcs, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, min_lines, arc_items,
-                     arc_shard_cap);
+    stroke_workgroup<CULL>(sh, arcs, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, stroke_lists, min_lines,
+                     arc_items, arc_shard_cap);
 }
 
 template <bool COOP, bool CULL>
 __global__ void __launch_bounds__(256, 2) k_flatten_heavy(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
                                                           const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
                                                           Control *control, LineSoup *lines, const uint32_t *__restrict__ heavy_list,
-                                                          uint32_t stroke_kernel_min_lines, const uint32_t *__restrict__ arc_items,
-                                                          uint32_t arc_shard_cap) {
+                                                          const uint32_t *__restrict__ stroke_lists, uint32_t stroke_kernel_min_lines,
+                                                          const uint32_t *__restrict__ arc_items, uint32_t arc_shard_cap) {
     __shared__ FlattenShared<FLATTEN_LDS_LINES> sh;
     __shared__ EulerCoopLds coop[COOP ? 4 : 1];
     heavy_workgroups<HEAVY_FIRST | HEAVY_SET_ASIDE, COOP, CULL>(sh, coop, blockIdx.x, gridDim.x, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list,
-                                                    stroke_kernel_min_lines, arc_items, arc_shard_cap);
+                                                    stroke_lists, stroke_kernel_min_lines, arc_items, arc_shard_cap);
+}
+
+// ---- indexed scenes (SceneIndex, ctx.h): the light pass over the index's fill list ----------------------------------------
+// k_scene_index_lists, once per upload: the sorting half of flatten_light_workgroup.  Every segment tag goes to one of three lists
+// ([3][n_tags], sections as heavy_list's: fill segments | stroked tags that are not lines | stroked lines), appended as the light
+// pass appends -- a wave's tags in tag order, the workgroup's behind one atomic per list -- so a path's tags stay in runs.
+__global__ void __launch_bounds__(256) k_scene_index_lists(Config cfg, uint32_t n_tags, const uint32_t *__restrict__ scene,
+                                                           const TagMonoid *__restrict__ tag_monoids, const Control *control, uint32_t *lists,
+                                                           uint32_t *counts) {
+    __shared__ uint32_t sh_list[3][FLATTEN_BLOCK_TAGS];
+    __shared__ uint32_t sh_n[3], sh_base[3];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if ((control->bump.failed & FAILED_SCENE) != 0u) return;  // the tag stream overruns the scene: nothing may be indexed with it
+    if (tid < 3u) sh_n[tid] = 0u;
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t j = 0; j < FLATTEN_TAGS_PER_THREAD; j++) {
+        const uint32_t ix = blockIdx.x * FLATTEN_BLOCK_TAGS + tid + j * 256u;
+        uint32_t kind = 0u;
+        if (ix < n_tags) kind = classify_tag(cfg, scene, compute_tag_monoid(cfg, scene, tag_monoids, ix));
+        // (list 0: TAG_FILL_SEGMENT, 1: HEAVY_STROKE, 2: HEAVY_STROKE_LINE)
+        const uint32_t which = kind == TAG_FILL_SEGMENT ? 0u : kind == HEAVY_STROKE ? 1u : kind == HEAVY_STROKE_LINE ? 2u : 3u;
+#pragma unroll
+        for (uint32_t k = 0; k < 3u; k++) {
+            const unsigned long long hm = __ballot(which == k);
+            if (hm != 0ull) {
+                const int leader = __ffsll((long long)hm) - 1;
+                uint32_t wbase = 0u;
+                if ((int)lane == leader) wbase = atomicAdd(&sh_n[k], (uint32_t)__popcll(hm));
+                wbase = (uint32_t)__shfl((int)wbase, leader);
+                if (which == k) sh_list[k][wbase + (uint32_t)__popcll(hm & ((1ull << lane) - 1ull))] = ix;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < 3u) sh_base[tid] = sh_n[tid] ? atomicAdd(&counts[tid], sh_n[tid]) : 0u;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++)
+        for (uint32_t i = tid; i < sh_n[k]; i += 256u) lists[(size_t)k * n_tags + sh_base[k] + i] = sh_list[k][i];
+}
+
+void launch_scene_index_lists(const Frame &f, uint32_t *lists, uint32_t *counts, hipStream_t s) {
+    const uint32_t n_tags = f.n_tag_words * 4u;
+    const uint32_t grid = (n_tags + FLATTEN_BLOCK_TAGS - 1u) / FLATTEN_BLOCK_TAGS;
+    if (grid == 0u) return;
+    hipLaunchKernelGGL(k_scene_index_lists, dim3(grid), dim3(256), 0, s, f.cfg, n_tags, f.scene, f.tag_monoids, f.control, lists, counts);
+}
+
+// One workgroup of the light pass of an indexed frame: FLATTEN_BLOCK_TAGS entries of the index's fill list from entry `block` x
+// FLATTEN_BLOCK_TAGS on.  Every entry is a fill's segment -- nothing is sorted here: one transform, one straightness test, one line,
+// or an entry of the frame's curve list (heavy_list section 0; sections 1 and 2 are the index's).
+struct LightListLds {
+    FlattenShared<FLATTEN_BLOCK_TAGS> sh;   // at most one line per entry: never overflows
+    uint32_t curves[FLATTEN_BLOCK_TAGS];
+    uint32_t n_curves, curves_base;
+};
+template <bool CULL>
+__device__ __forceinline__ void flatten_light_list_workgroup(LightListLds &s, const Config &cfg, uint32_t block, uint32_t n_list,
+                                                             const uint32_t *__restrict__ list, const uint32_t *scene, const TagMonoid *tag_monoids,
+                                                             PathBbox *path_bboxes, Control *control, LineSoup *lines, uint32_t *heavy_list) {
+    FlattenShared<FLATTEN_BLOCK_TAGS> &sh = s.sh;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    const uint32_t e0 = block * FLATTEN_BLOCK_TAGS + tid;
+    if ((control->bump.failed & FAILED_SCENE) != 0u) return;  // (such a scene's lists are empty: the host launches no such workgroup)
+    if (tid == 0u) {
+        sh.count = 0u;
+        sh.lds_end = 0xffffffffu;
+        if (CULL) sh.base = 0u;
+        s.n_curves = 0u;
+    }
+    __syncthreads();
+    Bump *bump = &control->bump;
+#pragma unroll 1
+    for (uint32_t j = 0; j < FLATTEN_TAGS_PER_THREAD; j++) {
+        Emitter em;
+        em.lines = lines;
+        em.lines_size = cfg.lines_size;
+        em.bump = bump;
+        em.bind(sh);
+        const uint32_t e = e0 + j * 256u;
+        uint32_t key = 0xffffffffu, ix = 0u;
+        float x0 = 1e31f, y0 = 1e31f, x1 = -1e31f, y1 = -1e31f;
+        bool curve = false;
+        if (e < n_list) {
+            ix = list[e];
+            const PathTagData tag = compute_tag_monoid(cfg, scene, tag_monoids, ix);
+            key = tag.monoid.path_ix;
+            em.bx0 = 1e31f; em.by0 = 1e31f; em.bx1 = -1e31f; em.by1 = -1e31f;
+            curve = flatten_fill_segment(em, cfg, scene, tag) == HEAVY_CURVE;
+            // a tag contributes only if it produced an extent (flatten.wgsl:915)
+            if (em.bx1 > em.bx0 || em.by1 > em.by0) {
+                x0 = em.bx0; y0 = em.by0; x1 = em.bx1; y1 = em.by1;
+            }
+        }
+        const unsigned long long hm = __ballot(curve);
+        if (hm != 0ull) {
+            const int leader = __ffsll((long long)hm) - 1;
+            uint32_t wbase = 0u;
+            if ((int)lane == leader) wbase = atomicAdd(&s.n_curves, (uint32_t)__popcll(hm));
+            wbase = (uint32_t)__shfl((int)wbase, leader);
+            if (curve) s.curves[wbase + (uint32_t)__popcll(hm & ((1ull << lane) - 1ull))] = ix;
+        }
+        wave_bbox_update(path_bboxes, cfg.layout.n_paths, key, x0, y0, x1, y1, (int)lane);
+    }
+    // (the workgroup's two reservations as one instruction of two lanes: flatten_light_workgroup says why)
+    __syncthreads();
+    const uint32_t n_lds = minu(sh.count, sh.lds_end);
+    const float cull_wt = (float)cfg.width_in_tiles, cull_ht = (float)cfg.height_in_tiles;
+    uint32_t wave_off = 0u;
+    if (CULL) {
+        wave_off = cull_count_staged(sh, n_lds, cull_wt, cull_ht, tid);
+        __syncthreads();
+    }
+    if (tid < 2u) {
+        uint32_t *const counter = tid == 0u ? &bump->lines : &control->heavy_count[0];
+        const uint32_t n = tid == 0u ? (CULL ? sh.base : n_lds) : s.n_curves;
+        const uint32_t got = n ? atomicAdd(counter, n) : 0u;
+        if (tid == 0u) sh.base = got;
+        else s.curves_base = got;
+    }
+    __syncthreads();
+    if (CULL) copy_kept_lines(sh, lines, cfg.lines_size, sh.base + wave_off, n_lds, cull_wt, cull_ht, tid);
+    else copy_staged_lines(sh, lines, cfg.lines_size, sh.base, n_lds, tid);
+    for (uint32_t i = tid; i < s.n_curves; i += 256u) heavy_list[s.curves_base + i] = s.curves[i];
+}
+
+// k_flatten_light of an indexed frame: the draw stage's workgroups first, as there.
+template <bool CULL>
+__global__ void __launch_bounds__(256, 4) k_flatten_light_list(Config cfg, uint32_t n_list, const uint32_t *__restrict__ list, const uint32_t *__restrict__ scene,
+                                                               const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes, Control *control,
+                                                               LineSoup *lines, uint32_t *heavy_list, uint32_t n_draw_blocks,
+                                                               unsigned long long *draw_state, DrawMonoid *__restrict__ draw_monoids,
+                                                               uint32_t *__restrict__ info, Clip *__restrict__ clip_inp) {
+    if (blockIdx.x < n_draw_blocks) {
+        draw_scan_workgroup(cfg, scene, control, draw_state, path_bboxes, draw_monoids, info, clip_inp);
+        return;
+    }
+    __shared__ LightListLds s;
+    flatten_light_list_workgroup<CULL>(s, cfg, blockIdx.x - n_draw_blocks, n_list, list, scene, tag_monoids, path_bboxes, control, lines, heavy_list);
+}
+
+// Frames in flight, an indexed frame: nothing the stroke workgroups read is the light pass's any more (their lists are the index's,
+// the lengths k_frame_begin's), so the two share the frame's first flatten launch -- in grid order the draw stage's workgroups, the
+// stroke workgroups (the longest: first), the light pass over the fill list -- and k_flatten_heavy follows.  One LDS block, laid out
+// per kind of workgroup as k_flatten_main's is: the kinds' sum would halve the workgroups a CU holds.
+constexpr size_t FLATTEN_FRONT_ARCS_AT = (sizeof(FlattenShared<FLATTEN_STROKE_ROUND_LINES>) + 15u) & ~(size_t)15u;
+constexpr size_t FLATTEN_FRONT_LDS = FLATTEN_FRONT_ARCS_AT + sizeof(ArcQueue) > sizeof(LightListLds) ? FLATTEN_FRONT_ARCS_AT + sizeof(ArcQueue) : sizeof(LightListLds);
+template <bool CULL>
+__global__ void __launch_bounds__(256) k_flatten_front(Config cfg, uint32_t n_tags, uint32_t n_list, const uint32_t *__restrict__ index_lists,
+                                                       const uint32_t *__restrict__ scene, const TagMonoid *__restrict__ tag_monoids, PathBbox *path_bboxes,
+                                                       Control *control, LineSoup *lines, uint32_t *heavy_list, uint32_t min_lines, uint32_t *arc_items,
+                                                       uint32_t arc_shard_cap, uint32_t n_draw_blocks, uint32_t n_stroke_blocks, unsigned long long *draw_state,
+                                                       DrawMonoid *__restrict__ draw_monoids, uint32_t *__restrict__ info, Clip *__restrict__ clip_inp) {
+    if (blockIdx.x < n_draw_blocks) {
+        draw_scan_workgroup(cfg, scene, control, draw_state, path_bboxes, draw_monoids, info, clip_inp);
+        return;
+    }
+    __shared__ __attribute__((aligned(16))) unsigned char smem[FLATTEN_FRONT_LDS];
+    const uint32_t block = blockIdx.x - n_draw_blocks;
+    if (block < n_stroke_blocks)
+        stroke_workgroup<CULL>(*reinterpret_cast<FlattenShared<FLATTEN_STROKE_ROUND_LINES> *>(smem), *reinterpret_cast<ArcQueue *>(smem + FLATTEN_FRONT_ARCS_AT), block,
+                               n_stroke_blocks, cfg, n_tags, scene, tag_monoids, path_bboxes, control, lines, heavy_list, index_lists, min_lines, arc_items,
+                               arc_shard_cap);
+    else
+        flatten_light_list_workgroup<CULL>(*reinterpret_cast<LightListLds *>(smem), cfg, block - n_stroke_blocks, n_list, index_lists, scene, tag_monoids,
+                                           path_bboxes, control, lines, heavy_list);
 }
 
 // ---- small scenes: consecutive stages as ONE launch ------------------------------------------------------------------
@@ -1835,7 +2015,7 @@ __global__ void __launch_bounds__(256) k_front(Config cfg, FrontArgs a) {
             if (ok)
             heavy_workgroups<HEAVY_FIRST, true, CULL>(*reinterpret_cast<FlattenShared<FLATTEN_LDS_LINES> *>(smem),
                                                 reinterpret_cast<EulerCoopLds *>(smem + FLATTEN_ARCS_AT), wg, n_wg, cfg, a.n_tags, a.scene, a.tag_monoids,
-                                                a.path_bboxes, a.control, a.lines, a.heavy_list, 0xffffffffu, a.arc_items, a.arc_shard_cap);
+                                                a.path_bboxes, a.control, a.lines, a.heavy_list, a.heavy_list, 0xffffffffu, a.arc_items, a.arc_shard_cap);
             FRONT_STAGE_END(FRONT_HEAVY);
         }
     }
@@ -1962,6 +2142,9 @@ uint32_t launch_front(const Frame &f, hipStream_t s, uint32_t stages, bool with_
     return barriers(stages);
 }
 
+#ifndef VK_INDEXED_MERGED_FRONT
+#define VK_INDEXED_MERGED_FRONT 1  // (A/B constant: 0 keeps an indexed frame's flatten in flight as three launches, list pass -> strokes -> heavy)
+#endif
 // (CULL = Frame::viewport_cull: the kernels' instantiations that leave lines off the target out of the soup)
 template <bool CULL>
 static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mid, bool with_draw_scan, bool light_done) {
@@ -1978,7 +2161,23 @@ static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mi
         return;
     }
     const uint32_t grid_draw = with_draw_scan ? (f.cfg.layout.n_draw_objects + DRAW_PART - 1u) / DRAW_PART : 0u;
-    if (!light_done)
+    // sections 1 and 2 of the lists: the frame's own, or the scene index's
+    const uint32_t *const stroke_lists = f.indexed ? f.index_lists : f.heavy_list;
+    const uint32_t grid_list = (f.index_n_fill + FLATTEN_BLOCK_TAGS - 1u) / FLATTEN_BLOCK_TAGS;  // (an indexed frame's light pass)
+    // (the stroke workgroups' launch arguments below: needed here already by a frame whose first launch holds them)
+    const uint32_t n_seg_max = flatten_n_seg_max(f);
+    const uint32_t grid_strokes = f.launch_stroke_kernel ? flatten_strokes_grid(n_seg_max, f.flatten_side_by_side) : 0u;
+    const uint32_t arc_shard_cap = flatten_arc_shard_cap(n_seg_max, f.flatten_side_by_side);
+    const bool front = f.indexed && !f.flatten_side_by_side && VK_INDEXED_MERGED_FRONT != 0 && grid_strokes != 0u;
+    if (front) {
+        hipLaunchKernelGGL(k_flatten_front<CULL>, dim3(grid_draw + grid_strokes + grid_list), dim3(256), 0, s, cx, n_tags, f.index_n_fill, f.index_lists, f.scene,
+                           f.tag_monoids, f.path_bboxes, f.control, f.lines, f.heavy_list, f.stroke_kernel_min_lines, f.arc_items, arc_shard_cap, grid_draw,
+                           grid_strokes, f.draw_state, f.draw_monoids, f.info_bin_data, f.clip_inp);
+    } else if (f.indexed) {
+        if (grid_draw + grid_list != 0u)
+            hipLaunchKernelGGL(k_flatten_light_list<CULL>, dim3(grid_draw + grid_list), dim3(256), 0, s, cx, f.index_n_fill, f.index_lists, f.scene, f.tag_monoids,
+                               f.path_bboxes, f.control, f.lines, f.heavy_list, grid_draw, f.draw_state, f.draw_monoids, f.info_bin_data, f.clip_inp);
+    } else if (!light_done)
         hipLaunchKernelGGL(k_flatten_light<CULL>, dim3(grid + grid_draw), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
                            f.lines, f.heavy_list, grid_draw, f.draw_state, f.draw_monoids, f.info_bin_data, f.clip_inp);
     if (mid) (void)hipEventRecord(mid[0], s);
@@ -1986,7 +2185,6 @@ static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mi
     // (workgroups beyond the list exit at once)
     // (a segment owns at least one word of path data, so the path-data stream bounds the list even though the tag stream
     // is padded to 4096 tags)
-    const uint32_t n_seg_max = flatten_n_seg_max(f);
     uint32_t grid_heavy = (n_seg_max + 3u) / 4u;
 #ifndef VK_FH_GRID_IN_FLIGHT
 #define VK_FH_GRID_IN_FLIGHT 2048u  // (sweep constant: the heavy workgroups' cap with frames in flight)
@@ -1996,16 +2194,14 @@ static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mi
     if (grid_heavy < 4u) grid_heavy = 4u;
     // (stroke workgroups leave at once when the scene has too few stroked lines for workgroups of their own; they are not
     // launched at all once a finished frame of the scene has shown that)
-    const uint32_t grid_strokes = f.launch_stroke_kernel ? flatten_strokes_grid(n_seg_max, f.flatten_side_by_side) : 0u;
-    const uint32_t arc_shard_cap = flatten_arc_shard_cap(n_seg_max, f.flatten_side_by_side);
     const uint32_t min_lines = f.launch_stroke_kernel ? f.stroke_kernel_min_lines : 0xffffffffu;  // (no stroke workgroups: every line is the heavy ones')
     if (f.flatten_side_by_side) {
         if (f.flatten_coop)
             hipLaunchKernelGGL((k_flatten_main<true, CULL>), dim3(grid_heavy + grid_strokes), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
-                               f.control, f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap, grid_heavy);
+                               f.control, f.lines, f.heavy_list, stroke_lists, min_lines, f.arc_items, arc_shard_cap, grid_heavy);
         else
             hipLaunchKernelGGL((k_flatten_main<false, CULL>), dim3(grid_heavy + grid_strokes), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
-                               f.control, f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap, grid_heavy);
+                               f.control, f.lines, f.heavy_list, stroke_lists, min_lines, f.arc_items, arc_shard_cap, grid_heavy);
         if (mid) (void)hipEventRecord(mid[1], s);
         // what the stroke workgroups set aside (arcs: a few per cent of the lines; handed-on lines: nearly none)
         if (grid_strokes != 0u) {
@@ -2016,16 +2212,16 @@ static void launch_flatten_kernels(const Frame &f, hipStream_t s, hipEvent_t *mi
                                f.lines, f.heavy_list, f.arc_items, arc_shard_cap);
         }
     } else {
-        if (grid_strokes != 0u)
+        if (grid_strokes != 0u && !front)  // (front: they rode in the first launch)
             hipLaunchKernelGGL(k_flatten_strokes<CULL>, dim3(grid_strokes), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes,
-                               f.control, f.lines, f.heavy_list, f.stroke_kernel_min_lines, f.arc_items, arc_shard_cap);
+                               f.control, f.lines, f.heavy_list, stroke_lists, f.stroke_kernel_min_lines, f.arc_items, arc_shard_cap);
         if (mid) (void)hipEventRecord(mid[1], s);
         if (f.flatten_coop)
             hipLaunchKernelGGL((k_flatten_heavy<true, CULL>), dim3(grid_heavy), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
-                               f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap);
+                               f.lines, f.heavy_list, stroke_lists, min_lines, f.arc_items, arc_shard_cap);
         else
             hipLaunchKernelGGL((k_flatten_heavy<false, CULL>), dim3(grid_heavy), dim3(256), 0, s, cx, n_tags, f.scene, f.tag_monoids, f.path_bboxes, f.control,
-                               f.lines, f.heavy_list, min_lines, f.arc_items, arc_shard_cap);
+                               f.lines, f.heavy_list, stroke_lists, min_lines, f.arc_items, arc_shard_cap);
     }
 }
 

@@ -249,6 +249,18 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
     f.pathtag_state = (unsigned long long *)((char *)l.zero_region.ptr + sizeof(Control));
     f.draw_state = f.pathtag_state + (size_t)sc.n_pathtag_parts * 10u;
     f.tag_monoids = (TagMonoid *)l.buf[VELLO_HIP_BUF_TAG_MONOIDS].ptr;
+    // a frame of the shared scene with an index (built by its upload; VELLO_HIP_DEBUG_NO_SCENE_INDEX: today's per-frame path): the
+    // scan's output and flatten's two stroke lists are the index's, read by every lane
+    const SceneIndex &ix = sc.index;
+    f.indexed = &sc == &c->shared && ix.valid && (c->debug_flags & VELLO_HIP_DEBUG_NO_SCENE_INDEX) == 0u;
+    f.index_bboxes = f.indexed ? (const PathBbox *)ix.bboxes.ptr : nullptr;
+    f.index_lists = f.indexed ? (const uint32_t *)ix.lists.ptr : nullptr;
+    f.index_n_fill = f.indexed ? ix.n_fill : 0u;
+    f.index_n_strokes = f.indexed ? ix.n_strokes : 0u;
+    f.index_n_lines = f.indexed ? ix.n_lines : 0u;
+    f.index_failed = f.indexed ? ix.failed : 0u;
+    if (f.indexed) f.tag_monoids = (TagMonoid *)ix.monoids.ptr;
+    l.frame_indexed = f.indexed;
     f.path_bboxes = (PathBbox *)l.buf[VELLO_HIP_BUF_PATH_BBOXES].ptr;
     f.lines = (LineSoup *)l.buf[VELLO_HIP_BUF_LINES].ptr;
     f.draw_monoids = (DrawMonoid *)l.buf[VELLO_HIP_BUF_DRAW_MONOIDS].ptr;
@@ -416,6 +428,10 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
                 break;
             }
             if (fuse_a) break;  // (with FLATTEN's first launch)
+            if (f.indexed) {  // (never a frame that was `zeroed`: those are the retained list's)
+                launch_frame_begin(f, st);
+                break;
+            }
             if (!zeroed) HIP_TRY(c, hipMemsetAsync(l.zero_region.ptr, 0, slot_of(c, l).zero_bytes, st));
             launch_pathtag_scan(f, st);
             break;

@@ -88,6 +88,7 @@ int size_slot(vello_hip_ctx *c, SceneSlot &sc, const vello_hip_layout &L, size_t
     sc.soup_lines = -1;
     sc.slice_demand = -1;
     sc.generation += 1u;
+    sc.index.valid = false;  // (it spoke for the bytes the slot held)
     return VELLO_HIP_OK;
 }
 
@@ -284,6 +285,52 @@ int launch_compose(vello_hip_ctx *c, const ComposePlan &p, uint32_t n, bool pain
     return 0;
 }
 
+// The index of the shared scene (SceneIndex, ctx.h), built where the upload already blocks: the pathtag scan into the index's
+// arrays -- with lane 0's zero region, which is idle and sized for the scene, as its control block and look-back state -- then
+// k_scene_index_lists, and the lengths and the verdict read back.  Scenes small enough for k_front are not indexed: their stages
+// share launches, and launches are what they cost.  A scan whose look-back gave up leaves the scene without an index.
+int build_scene_index(vello_hip_ctx *c) {
+    SceneSlot &sc = c->shared;
+    const vello_hip_layout &L = sc.layout;
+    SceneIndex &ix = sc.index;
+    ix.valid = false;
+    if ((sc.n_tag_words * 4u <= FRONT_MAX_TAGS && L.n_draw_objects <= FRONT_MAX_DRAW_OBJECTS && L.n_paths <= FRONT_MAX_DRAW_OBJECTS) ||
+        L.n_paths > 0x40000000u)  // (k_frame_begin counts the boxes in 8-byte words)
+        return 0;
+    Lane &l = c->lanes[0];
+    hipStream_t st = l.stream;
+    const size_t n_tags = (size_t)sc.n_tag_words * 4u;
+    int r;
+    if ((r = ensure(c, ix.monoids, (size_t)(sc.n_tag_words + 4u) * sizeof(TagMonoid)))) return r;
+    if ((r = ensure(c, ix.bboxes, (size_t)(L.n_paths + 1u) * sizeof(PathBbox)))) return r;
+    if ((r = ensure(c, ix.lists, 3u * n_tags * 4u))) return r;
+    if ((r = ensure(c, ix.counts, 16))) return r;
+    Frame f{};
+    std::memcpy(&f.cfg.layout, &L, sizeof(Layout));
+    f.n_tag_words = sc.n_tag_words;
+    f.n_scene_words = (uint32_t)(sc.scene_len / 4u);
+    f.scene = (const uint32_t *)sc.scene.ptr;
+    f.control = (Control *)l.zero_region.ptr;
+    f.pathtag_state = (unsigned long long *)((char *)l.zero_region.ptr + sizeof(Control));
+    f.tag_monoids = (TagMonoid *)ix.monoids.ptr;
+    f.path_bboxes = (PathBbox *)ix.bboxes.ptr;
+    HIP_TRY(c, hipMemsetAsync(l.zero_region.ptr, 0, sc.zero_bytes, st));
+    HIP_TRY(c, hipMemsetAsync(ix.counts.ptr, 0, 16, st));
+    launch_pathtag_scan(f, st);
+    launch_scene_index_lists(f, (uint32_t *)ix.lists.ptr, (uint32_t *)ix.counts.ptr, st);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    uint32_t counts[4], failed = 0u;
+    HIP_TRY(c, hipMemcpy(counts, ix.counts.ptr, sizeof counts, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&failed, l.zero_region.ptr, 4, hipMemcpyDeviceToHost));  // (bump.failed: the control block's first word)
+    if ((failed & ~FAILED_SCENE) != 0u) return 0;
+    ix.failed = failed;
+    ix.n_fill = counts[0], ix.n_strokes = counts[1], ix.n_lines = counts[2];
+    ix.valid = true;
+    c->scene_index_builds++;
+    return 0;
+}
+
 }  // namespace
 
 namespace vk {
@@ -360,10 +407,16 @@ int vello_hip_upload_scene(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
         l.which = LaneScene::Shared;
         if ((r = alloc_lane_scene(c, l, c->shared))) return r;
     }
+    // (the lanes are idle and sized for the scene: the index's scan borrows lane 0's zero region)
+    if ((r = build_scene_index(c))) {
+        c->shared.resident = false;
+        return r;
+    }
     return VELLO_HIP_OK;
 }
 
 uint64_t vello_hip_scene_allocations(vello_hip_ctx *c) { return c ? c->scene_allocations : 0u; }
+uint64_t vello_hip_scene_index_builds(vello_hip_ctx *c) { return c ? c->scene_index_builds : 0u; }
 
 int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout, const uint32_t *ramps,
                                uint32_t n_ramps, const vello_hip_fragment *frags, uint32_t n_frags) {

@@ -63,6 +63,9 @@ BufView find_buf(vello_hip_ctx *c, int id) {
     Lane &l = c->lanes[c->last_lane];
     // (the bump allocators first, then the engine's own counters: the head of the lane's zero region)
     if (id == VELLO_HIP_BUF_BUMP) return {l.zero_region.ptr, l.zero_region.ptr ? sizeof(Control) : 0u};
+    // (a frame of an indexed scene read the index's tag monoids, not its lane's)
+    if (id == VELLO_HIP_BUF_TAG_MONOIDS && l.frame_indexed && l.which == LaneScene::Shared && c->shared.index.valid)
+        return {c->shared.index.monoids.ptr, c->shared.index.monoids.size};
     const DevBuf &b = id == VELLO_HIP_BUF_SCENE ? slot_of(c, l).scene : id == VELLO_HIP_BUF_CONFIG ? c->config : l.buf[id];
     return {b.ptr, b.size};
 }
@@ -95,6 +98,9 @@ int access_buffer(vello_hip_ctx *c, int id, void *host, size_t offset, size_t si
     int r = sync_all(c);
     if (r) return r;
     if (id == VELLO_HIP_BUF_CONFIG && (r = send_config(c))) return r;
+    // (bytes written into an indexed scene: its index speaks for the bytes of the upload -- the frames from here on take the
+    // per-frame path, until the next upload builds a new one)
+    if (write && id == VELLO_HIP_BUF_SCENE && &slot_of(c, c->lanes[c->last_lane]) == &c->shared) c->shared.index.valid = false;
     if (write) HIP_TRY(c, hipMemcpy((char *)b.ptr + offset, host, size, hipMemcpyHostToDevice));
     else HIP_TRY(c, hipMemcpy(host, (const char *)b.ptr + offset, size, hipMemcpyDeviceToHost));
     return VELLO_HIP_OK;

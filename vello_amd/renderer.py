@@ -755,20 +755,22 @@ class Engine:
         self._check(self._lib.vello_hip_set_view_transform(self._h, _view_floats(view)), "set_view_transform")
 
     def set_debug_flags(self, no_cull=False, stroke_kernel=False, seq_clip=False, fine_slices=False, flatten_coop=False, flatten_alone=False, no_fusion=False,
-                        pick_small_batches=False):
+                        pick_small_batches=False, no_scene_index=False):
         """vello_hip_set_debug_flags: no_cull makes coarse emit every draw (reference-exact PTCL / segments); stroke_kernel
         runs flatten's stroked-line kernel whatever the number of stroked lines; seq_clip matches clips with the one-wave
         stack machine instead of the partitioned kernels; fine_slices cuts every tile's command list into slices of
         4 fills for fine's MSAA modes (normally only lists of >= 96 fills are cut, engine.h FINE_SLICE_MIN_FILLS); flatten_coop /
         flatten_alone pick the kernels of flatten's heavy list (the wave-cooperative walk / every lane on its own) instead of leaving
         the choice to the engine; no_fusion launches every stage of a small scene as a kernel of its own (normally consecutive stages
-        up to tile_alloc share launches there); pick_small_batches answers a pick's queries three at a time.  Flags not named are cleared (update_debug_flags keeps them)."""
+        up to tile_alloc share launches there); pick_small_batches answers a pick's queries three at a time; no_scene_index renders a resident scene
+        without the index its upload built (scene_index_builds): the per-frame scan and whole-stream light pass.  Flags not named are cleared (update_debug_flags keeps them)."""
         self._debug = {"no_cull": bool(no_cull), "stroke_kernel": bool(stroke_kernel), "seq_clip": bool(seq_clip),
                        "fine_slices": bool(fine_slices), "flatten_coop": bool(flatten_coop), "flatten_alone": bool(flatten_alone),
-                       "no_fusion": bool(no_fusion), "pick_small_batches": bool(pick_small_batches)}
+                       "no_fusion": bool(no_fusion), "pick_small_batches": bool(pick_small_batches), "no_scene_index": bool(no_scene_index)}
         d = self._debug
         flags = ((1 if d["no_cull"] else 0) | (2 if d["stroke_kernel"] else 0) | (4 if d["seq_clip"] else 0) | (8 if d["fine_slices"] else 0) |
-                 (16 if d["flatten_coop"] else 0) | (32 if d["flatten_alone"] else 0) | (64 if d["no_fusion"] else 0) | (128 if d["pick_small_batches"] else 0))
+                 (16 if d["flatten_coop"] else 0) | (32 if d["flatten_alone"] else 0) | (64 if d["no_fusion"] else 0) | (128 if d["pick_small_batches"] else 0) |
+                 (256 if d["no_scene_index"] else 0))
         self._check(self._lib.vello_hip_set_debug_flags(self._h, flags), "set_debug_flags")
 
     def update_debug_flags(self, **changes):
@@ -787,6 +789,11 @@ class Engine:
     def scene_allocations(self):
         """vello_hip_scene_allocations: scene buffers allocated since the engine was created."""
         return int(self._lib.vello_hip_scene_allocations(self._h))
+
+    def scene_index_builds(self):
+        """vello_hip_scene_index_builds: scene indexes built since the engine was created (one per upload of a scene too large for the
+        small-scene launches; frames build none)."""
+        return int(self._lib.vello_hip_scene_index_builds(self._h))
 
     def set_frames_in_flight(self, n):
         self._check(self._lib.vello_hip_set_frames_in_flight(self._h, n), "set_frames_in_flight")
