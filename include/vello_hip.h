@@ -683,8 +683,24 @@ int vello_hip_set_debug_flags(vello_hip_ctx *ctx, uint32_t flags);
 
 /* Number of frames the context keeps in flight (default 1, max 8).  wgpu queues recordings without waiting
  * (wgpu_engine.rs:757); with n > 1 consecutive vello_hip_render_resident calls rotate over n private buffer
- * sets and streams and overlap on the GPU.  The caller must hand each in-flight frame its own target. */
+ * sets and streams and overlap on the GPU.  The caller must hand each in-flight frame its own target.
+ *
+ * Frames overlap only where their streams dispatch on different hardware queues.  The HIP runtime keeps a pool of hardware queues
+ * per stream priority, each capped on its own (GPU_MAX_HW_QUEUES, 4 by default), and gives a new stream a new queue of its pool
+ * until the cap, then the queue with the fewest streams.  When the device has a range of stream priorities the context therefore
+ * creates its frames' streams with ONE priority that is not the default's (the greatest), so that up to as many frames in flight
+ * as the cap allows have a hardware queue each whatever the process's other streams -- the null stream, the caller's, the
+ * context's own upload and copy streams -- hold in the default pool; more frames in flight than the cap share queues by the
+ * runtime's rule.  Without a range, or when such a stream cannot be created, the streams are of the default priority.  The
+ * environment variable VELLO_HIP_DEBUG_LANE_QUEUES, read once by vello_hip_create, is the A/B seam: `default` creates the streams
+ * with the default priority (hipStreamCreateWithFlags), `least` / `greatest` pick that end of the device's range; any other value
+ * fails vello_hip_create with VELLO_HIP_E_INVALID. */
 int vello_hip_set_frames_in_flight(vello_hip_ctx *ctx, uint32_t n);
+/* The stream priority of frame lane `lane` (0 <= lane < the greatest number of frames in flight set so far), as
+ * hipStreamGetPriority reports it, and the device's range as hipDeviceGetStreamPriorityRange does (a numerically LOWER value is a
+ * greater priority; least == greatest: the device has none).  Read-only; any of the three pointers may be NULL.  Lets a test see
+ * the placement rule above without a profiler.  VELLO_HIP_E_INVALID for a lane the context has not created. */
+int vello_hip_lane_stream_priority(vello_hip_ctx *ctx, uint32_t lane, int *priority, int *device_least, int *device_greatest);
 /* Waits for the frame enqueued `age` vello_hip_render_resident calls ago (0 = newest, age < frames in flight)
  * without draining the younger ones; does not inspect bump.failed (vello_hip_sync does). */
 int vello_hip_sync_frame(vello_hip_ctx *ctx, uint32_t age);

@@ -126,6 +126,7 @@ def load_library():
     sig("vello_hip_stage_constant", u32, [i32])
     sig("vello_hip_pick_ms", i32, [vp, c.POINTER(c.c_float)])
     sig("vello_hip_set_frames_in_flight", i32, [vp, u32])
+    sig("vello_hip_lane_stream_priority", i32, [vp, u32, c.POINTER(i32), c.POINTER(i32), c.POINTER(i32)])
     sig("vello_hip_resize_image_atlas", i32, [vp, u32, u32])
     sig("vello_hip_write_image", i32, [vp, u32, u32, u32, u32, vp, sz])
     sig("vello_hip_copy_images_device", i32, [vp, c.POINTER(ImageCopyStruct), u32, vp])

@@ -1,5 +1,7 @@
 // The context's life and its memory: create and destroy, frames in flight, the pools' capacities and their growth, a lane's buffers.
 #include <array>
+#include <cstdlib>
+#include <cstring>
 
 #include "ctx.h"
 
@@ -31,8 +33,50 @@ std::array<Pool, 9> lane_pools(Lane &l, const vello_hip_capacities &d, uint32_t 
              {l.cov, cov_cap_words(d, aa_mask), 4u}}};
 }
 
+// What VELLO_HIP_DEBUG_LANE_QUEUES asks for (vello_hip.h, vello_hip_set_frames_in_flight)
+enum class LaneQueues { Greatest, Least, Default, Unknown };
+LaneQueues lane_queues_from_env() {
+    const char *v = std::getenv("VELLO_HIP_DEBUG_LANE_QUEUES");
+    if (!v || !*v || !std::strcmp(v, "greatest")) return LaneQueues::Greatest;
+    if (!std::strcmp(v, "least")) return LaneQueues::Least;
+    if (!std::strcmp(v, "default")) return LaneQueues::Default;
+    return LaneQueues::Unknown;
+}
+
+// The priority of the lanes' streams (ctx::lane_own_pool, ::lane_priority).  A device without a range, or a runtime that fails the
+// query, leaves the default.
+void choose_lane_priority(vello_hip_ctx *c, LaneQueues want) {
+    c->lane_own_pool = false;
+    c->lane_priority = 0;
+#ifndef VELLO_SIMT_EMU  // (the emulator has no queues)
+    if (want == LaneQueues::Default) return;
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    if (least == greatest) return;
+    c->lane_own_pool = true;
+    c->lane_priority = want == LaneQueues::Least ? least : greatest;
+#endif
+}
+
+int create_lane_stream(vello_hip_ctx *c, Lane &l) {
+#ifndef VELLO_SIMT_EMU
+    if (c->lane_own_pool) {
+        if (hipStreamCreateWithPriority(&l.stream, hipStreamNonBlocking, c->lane_priority) == hipSuccess) return 0;
+        (void)hipGetLastError();  // (sticky otherwise: the next HIP_TRY would report it)
+        l.stream = nullptr;
+        c->lane_own_pool = false;  // the lanes still to come are created as this one is
+    }
+#endif
+    HIP_TRY(c, hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
+    return 0;
+}
+
 int alloc_lane_pools(vello_hip_ctx *c, Lane &l) {
-    if (!l.stream) HIP_TRY(c, hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
+    if (!l.stream)
+        if (int r = create_lane_stream(c, l)) return r;
     for (const Pool &p : lane_pools(l, c->caps, c->aa_mask))
         if (int r = ensure(c, p.buf, p.count * p.elem)) return r;
     return 0;
@@ -184,6 +228,11 @@ const char *vello_hip_last_error(vello_hip_ctx *ctx) { return ctx ? ctx->last_er
 int vello_hip_create(int device, uint32_t aa_mask, const vello_hip_capacities *caps, vello_hip_ctx **out) {
     if (!out) return VELLO_HIP_E_INVALID;
     *out = nullptr;
+    const LaneQueues lane_queues = lane_queues_from_env();
+    if (lane_queues == LaneQueues::Unknown) {
+        g_create_error = "VELLO_HIP_DEBUG_LANE_QUEUES is none of default, least, greatest";
+        return VELLO_HIP_E_INVALID;
+    }
     int n_dev = 0;
     hipError_t e = hipGetDeviceCount(&n_dev);
     if (e != hipSuccess || n_dev <= 0 || device < 0 || device >= n_dev) {
@@ -199,7 +248,8 @@ int vello_hip_create(int device, uint32_t aa_mask, const vello_hip_capacities *c
     // renders 8 % fewer frames per second than one whose lanes come second to fifth (profiles/r06_queue_order.txt: 2 110 against
     // 2 300 on the road map, rocprofv3's Queue_Id per stream).  HIP hands out hardware queues in the order streams are created,
     // and creates the null stream's lazily -- so the null stream is made to take its queue here, before the lanes' streams exist
-    // (a caller that has used the device before gets the same order by itself).
+    // (a caller that has used the device before gets the same order by itself).  Lanes with a priority of their own
+    // (choose_lane_priority) sit in another pool of queues altogether; this claim is what lanes of the default priority rely on.
     {
         void *scratch = nullptr;
         if (hipMalloc(&scratch, 256) == hipSuccess) {
@@ -226,6 +276,7 @@ int vello_hip_create(int device, uint32_t aa_mask, const vello_hip_capacities *c
     // path_tiling writes segments[] unguarded by a failure bit only when both pools match (coarse.wgsl:166)
     if (d.segments < d.seg_counts) d.segments = d.seg_counts;
     c->caps = d;
+    choose_lane_priority(c, lane_queues);
     auto fail = [&](const char *what) {
         g_create_error = std::string(what) + ": " + c->last_error;
         vello_hip_destroy(c);
@@ -326,6 +377,20 @@ int vello_hip_set_frames_in_flight(vello_hip_ctx *c, uint32_t n) {
     c->n_active = n;  // shrinking keeps the extra lanes' buffers; only the rotation changes
     c->next_lane = 0;
     c->last_lane = 0;
+    return VELLO_HIP_OK;
+}
+
+int vello_hip_lane_stream_priority(vello_hip_ctx *c, uint32_t lane, int *priority, int *device_least, int *device_greatest) {
+    if (!c || lane >= c->lanes.size() || !c->lanes[lane].stream) return VELLO_HIP_E_INVALID;
+    int p = 0, least = 0, greatest = 0;
+#ifndef VELLO_SIMT_EMU  // (the emulator has no queues: one priority, 0)
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamGetPriority(c->lanes[lane].stream, &p));
+    HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+#endif
+    if (priority) *priority = p;
+    if (device_least) *device_least = least;
+    if (device_greatest) *device_greatest = greatest;
     return VELLO_HIP_OK;
 }
 

@@ -203,6 +203,11 @@ struct vello_hip_ctx {
     vk::DevBuf atlas;  // persistent image atlas (render.rs:160-176), shared by all lanes
     uint32_t atlas_w = 0, atlas_h = 0;
     std::vector<vk::Lane> lanes;
+    // The lanes' streams have ONE stream priority that is not the default's when the device has a range: the runtime keeps a pool of
+    // hardware queues per priority, so the lanes do not share queues with the null stream or the caller's streams.
+    // Chosen once by vello_hip_create; false: hipStreamCreateWithFlags (no range, a failed creation, VELLO_HIP_DEBUG_LANE_QUEUES=default)
+    bool lane_own_pool = false;
+    int lane_priority = 0;
     uint32_t n_active = 1;  // lanes in the rotation (<= lanes.size(): shrinking keeps the buffers)
     uint32_t next_lane = 0, last_lane = 0;
     bool auto_grow = false;

@@ -799,6 +799,15 @@ class Engine:
         self._check(self._lib.vello_hip_set_frames_in_flight(self._h, n), "set_frames_in_flight")
         self.KERNELS = dict(self.KERNELS, flatten=self.FLATTEN_KERNELS[0 if n == 1 else 1])
 
+    def lane_stream_priority(self, lane):
+        """vello_hip_lane_stream_priority: (priority of frame lane `lane`'s stream, the device's least priority, its greatest); a
+        numerically lower value is a greater priority.  The lanes of a context share one priority, not the default's when the device
+        has a range: a pool of hardware queues of their own (VELLO_HIP_DEBUG_LANE_QUEUES=default in the environment: the default's)."""
+        p, least, greatest = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._lib.vello_hip_lane_stream_priority(self._h, lane, ctypes.byref(p), ctypes.byref(least), ctypes.byref(greatest)),
+                    "lane_stream_priority")
+        return p.value, least.value, greatest.value
+
     def stream(self):
         """vello_hip_get_stream: the hipStream_t (as an int) of the lane that rendered the newest frame."""
         return int(self._lib.vello_hip_get_stream(self._h) or 0)
