@@ -642,13 +642,22 @@ int vello_hip_pick_rect(vello_hip_ctx *ctx, const float rect[4] /* x0 y0 x1 y1, 
  * per workgroup of binning, tile_alloc and coarse's prepass; draw objects per batch of k_coarse and the number of bins its grid is
  * rounded up to; lines per chunk of path_count's three forms (soup size unknown with one frame in flight, soup known to be small,
  * frames in flight); SegmentCounts per workgroup of path_tiling; tiles per block of backdrop's row scan; the most tags and draw
- * objects (paths) of a scene whose front stages share launches, and the most segments of one whose front is ONE launch.  0 for any
- * other `which`. */
+ * objects (paths) of a scene whose front stages share launches, and the most segments of one whose front is ONE launch.  Then
+ * fine's: the command words k_fine reads at a time; the fills, segments and crossing records a batch of fills holds at most; the
+ * most records of a fill that takes the straight-line replay; how many words behind a prefetched window's base the list may resume
+ * for the window to be used; the fills per slice of a long tile and the fills from which a tile is sliced (one frame in flight,
+ * frames in flight; both under VELLO_HIP_DEBUG_FINE_SLICES); the command words from which a tile counts as heavy; the words per
+ * bucket and the buckets of fine's tile order; the words of a tile's fixed command block.  0 for any other `which`. */
 enum { VELLO_HIP_SHAPE_PATHTAG_PART_TAGS = 0, VELLO_HIP_SHAPE_FLATTEN_BLOCK_TAGS = 1, VELLO_HIP_SHAPE_DRAW_PART = 2, VELLO_HIP_SHAPE_CLIP_PART = 3,
        VELLO_HIP_SHAPE_DRAW_WORKGROUP = 4, VELLO_HIP_SHAPE_COARSE_BATCH = 5, VELLO_HIP_SHAPE_COARSE_GRID_BINS = 6,
        VELLO_HIP_SHAPE_PATH_COUNT_CHUNK = 7, VELLO_HIP_SHAPE_PATH_COUNT_CHUNK_SMALL = 8, VELLO_HIP_SHAPE_PATH_COUNT_CHUNK_IN_FLIGHT = 9,
        VELLO_HIP_SHAPE_PATH_TILING_WORKGROUP = 10, VELLO_HIP_SHAPE_BACKDROP_BLOCK_TILES = 11, VELLO_HIP_SHAPE_FRONT_MAX_TAGS = 12,
-       VELLO_HIP_SHAPE_FRONT_MAX_DRAW_OBJECTS = 13, VELLO_HIP_SHAPE_FRONT_TINY_SEGMENTS = 14, VELLO_HIP_SHAPE_COUNT = 15 };
+       VELLO_HIP_SHAPE_FRONT_MAX_DRAW_OBJECTS = 13, VELLO_HIP_SHAPE_FRONT_TINY_SEGMENTS = 14,
+       VELLO_HIP_SHAPE_FINE_WINDOW_WORDS = 15, VELLO_HIP_SHAPE_FINE_BATCH_FILLS = 16, VELLO_HIP_SHAPE_FINE_BATCH_SEGMENTS = 17,
+       VELLO_HIP_SHAPE_FINE_ITEM_CAP = 18, VELLO_HIP_SHAPE_FINE_SIMPLE_RECORDS = 19, VELLO_HIP_SHAPE_FINE_PREFETCH_REACH = 20,
+       VELLO_HIP_SHAPE_FINE_SLICE_FILLS = 21, VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS = 22, VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS_IN_FLIGHT = 23,
+       VELLO_HIP_SHAPE_FINE_SLICE_FILLS_FORCED = 24, VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS_FORCED = 25, VELLO_HIP_SHAPE_FINE_HEAVY_WORDS = 26,
+       VELLO_HIP_SHAPE_FINE_BUCKET_WORDS = 27, VELLO_HIP_SHAPE_FINE_BUCKETS = 28, VELLO_HIP_SHAPE_PTCL_INITIAL_ALLOC = 29, VELLO_HIP_SHAPE_COUNT = 30 };
 uint32_t vello_hip_stage_constant(int which);
 
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a

@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(WG) k_coarse(Config cfg, const uint32_t *__res
         // ... and the tile's index in the bucket of its length class, so that long lists are started first (one atomic
         // per bucket and workgroup: 10 000 tiles bumping eight counters one by one cost the kernel 50 us)
         const uint32_t n_tiles = cfg.width_in_tiles * cfg.height_in_tiles;
-        uint32_t bucket = in_target ? minu(FINE_WORK_BUCKETS - 1u, words_total >> 5) : NONE;
+        uint32_t bucket = in_target ? minu(FINE_WORK_BUCKETS - 1u, words_total / FINE_BUCKET_WORDS) : NONE;
         // A long list (MSAA modes) is cut into slices of slice_fills FILLs, each a work item of fine's that comes before all
         // unsliced tiles; the tile then stays out of the buckets.  One atomic per counter and workgroup; a tile whose slices or
         // coverage scratch do not fit is rendered unsliced, its place in the item array marked as a hole.

@@ -36,7 +36,8 @@ constexpr uint32_t FAILED_INTERNAL = 0x80000000u;  // set in bump.failed when a 
 // than the scene buffer / layout hold (WebGPU's robust buffer access makes this harmless upstream; HIP has none):
 // every later stage that would index with those counts bails out, the frame reports VELLO_HIP_E_INVALID
 constexpr uint32_t FAILED_SCENE = 0x40000000u;
-constexpr uint32_t FINE_WORK_BUCKETS = 32;  // buckets of 32 command words (the last one: 992 and more)
+constexpr uint32_t FINE_WORK_BUCKETS = 32;  // buckets of FINE_BUCKET_WORDS command words (the last one: 992 and more)
+constexpr uint32_t FINE_BUCKET_WORDS = 32;
 // Stroked lines get workgroups of their own (beside the heavy list's in k_flatten_main with one frame in flight, as
 // k_flatten_strokes ahead of k_flatten_heavy with several) once they alone fill the chip twice over at 12 waves per CU
 // (256 CUs x 12 x 64 lanes); below that they are entries of the heavy list, whose duration the curves set anyway.
@@ -331,6 +332,12 @@ uint32_t coarse_grid_bins();            // coarse.hip: k_coarse's grid holds a m
 uint32_t path_count_chunk(int form);    // path.hip: lines per chunk -- 0: soup size unknown, one frame in flight; 1: small soup; 2: frames in flight
 uint32_t path_tiling_workgroup();       // path.hip: SegmentCounts per workgroup and turn
 uint32_t backdrop_block_tiles();        // path.hip BACKDROP_BLOCK_TILES
+uint32_t fine_window_words();           // fine.hip: command words k_fine reads at a time, a lane each
+uint32_t fine_batch_fills();            // fine.hip MS_BATCH_FILLS: fills a batch holds at most
+uint32_t fine_batch_segments();         // fine.hip: segments the fills of a batch hold at most (one 64-lane load)
+uint32_t fine_item_cap();               // fine.hip MS_ITEM_CAP: crossing records a batch holds at most
+uint32_t fine_simple_records();         // fine.hip: the most records of a fill that ms_fill_simple takes
+uint32_t fine_prefetch_reach();         // fine.hip: words behind a prefetched window's base at which the list may resume for it to be used
 
 // Device-to-atlas copies (vello_hip_copy_images_device, atlas.hip; k_atlas_copy, scene_ops.hip): one rectangle of raw RGBA8 words per entry.  `first` is
 // the exclusive prefix of width * height over the batch, so the batch is one concatenated texel space that k_atlas_copy

@@ -237,6 +237,14 @@ __device__ void fill_path_area(FineShared &sh, const Segment *__restrict__ segme
 // one count/scan, one dense item pass writing records to LDS; each FILL command then only replays its records
 // (ms_apply) and resolves.  Every integer operation on the counters is the reference's, so coverage is bit-identical.
 constexpr uint32_t MS_BATCH_FILLS = 12u;    // fills per batch (their segments must fit one 64-lane load)
+constexpr uint32_t MS_BATCH_SEGMENTS = 64u; // segments per batch: a lane each
+constexpr uint32_t MS_SIMPLE_RECORDS = 64u; // crossing records of a fill ms_fill_simple may take: a lane each
+// The command window (k_fine, blend_pass): a word per lane.  A command is decoded from the window only where all its words lie
+// inside it: the last position at which a FILL (4 words) or a COLOR (2 words) may begin.  A window requested ahead for the next
+// batch is taken while the list resumes at most FINE_PREFETCH_REACH words behind its base.
+constexpr uint32_t FINE_WINDOW_WORDS = 64u, FINE_FILL_LAST_POS = FINE_WINDOW_WORDS - 4u, FINE_COLOR_LAST_POS = FINE_WINDOW_WORDS - 2u;
+constexpr uint32_t FINE_PREFETCH_REACH = 8u;
+static_assert(FINE_WINDOW_WORDS == PTCL_INITIAL_ALLOC, "a tile's fixed block is exactly one window");
 static_assert(MS_BATCH_FILLS <= 16u, "the slot search of ms_build_batch covers 16 slots");
 static_assert(MS_BATCH_FILLS == sizeof(PixelLds::zero_at) / sizeof(PixelLds::zero_at[0]), "a row of PixelLds::zero_at per staged fill");
 static_assert(sizeof(PixelLds) <= sizeof(SegSetupLds), "PixelLds lives in SegSetupLds's storage");
@@ -597,7 +605,7 @@ __device__ uint32_t ms_build_batch(FineShared &sh, FineBatch &bt, const Segment 
     else if (win == CMD_COLOR || win == CMD_IMAGE) sz = 2u;
     else if (win == CMD_SOLID || win == CMD_BEGIN_CLIP) sz = 1u;
     else if (win == CMD_END_CLIP || win == CMD_LIN_GRAD || win == CMD_RAD_GRAD || win == CMD_SWEEP_GRAD || win == CMD_BLUR_RECT) sz = 3u;
-    const bool stop_here = sz == 0u || lane > 60u;  // (the walk went on only while ix + 4 <= window end)
+    const bool stop_here = sz == 0u || lane > FINE_FILL_LAST_POS;  // (the walk went on only while ix + 4 <= window end)
     uint32_t jump = stop_here ? lane : minu(lane + sz, 63u);
     uint32_t pos = s0;
 #pragma unroll
@@ -609,12 +617,12 @@ __device__ uint32_t ms_build_batch(FineShared &sh, FineBatch &bt, const Segment 
     // lane k: the k-th command of the list sits at `pos`
     const uint32_t tag_k = wave_shfl(win, pos);
     const uint32_t rule_k = wave_shfl(win, minu(pos + 1u, 63u));
-    bool is_fill = tag_k == CMD_FILL && pos <= 60u;
+    bool is_fill = tag_k == CMD_FILL && pos <= FINE_FILL_LAST_POS;
     const uint32_t segs_k = is_fill ? rule_k >> 1 : 0u;
     const uint32_t seg_incl = wave_incl_scan_u32(segs_k, (int)lane);
     // the batch ends in front of the first FILL whose segments no longer fit, and after MS_BATCH_FILLS fills
     unsigned long long fills = __ballot(is_fill);
-    const unsigned long long over = __ballot(is_fill && seg_incl > 64u);
+    const unsigned long long over = __ballot(is_fill && seg_incl > MS_BATCH_SEGMENTS);
     if (over != 0ull) fills &= (1ull << (__ffsll((long long)over) - 1)) - 1ull;
     uint32_t n = (uint32_t)__popcll(fills);
     if (n > MS_BATCH_FILLS) {
@@ -645,7 +653,7 @@ __device__ uint32_t ms_build_batch(FineShared &sh, FineBatch &bt, const Segment 
     // regular prefix: command k (lane k) is a kept FILL for even k and a CMD_COLOR inside the window for odd k
     uint32_t pairs;
     {
-        const bool ok = (lane & 1u) != 0u ? (tag_k == CMD_COLOR && pos <= 62u) : ((fills >> lane) & 1ull) != 0ull;
+        const bool ok = (lane & 1u) != 0u ? (tag_k == CMD_COLOR && pos <= FINE_COLOR_LAST_POS) : ((fills >> lane) & 1ull) != 0ull;
         const unsigned long long bad = __ballot(!ok);
         pairs = (bad ? (uint32_t)__ffsll((long long)bad) - 1u : 64u) >> 1;
     }
@@ -704,7 +712,7 @@ __device__ uint32_t ms_build_batch(FineShared &sh, FineBatch &bt, const Segment 
         uint32_t my_begin = wave_shfl(my_end, lane - 1u & 63u);  // (only lanes < 12 matter)
         if (lane == 0u) my_begin = 0u;
         // the staged fills ms_fill_simple may take: non-zero rule, 1 .. 64 crossing records
-        simple_mask = (uint32_t)__ballot(lane < n_fit && (my_rule_n & 1u) == 0u && my_end - my_begin - 1u < 64u);
+        simple_mask = (uint32_t)__ballot(lane < n_fit && (my_rule_n & 1u) == 0u && my_end - my_begin - 1u < MS_SIMPLE_RECORDS);
         slots.pack = (my_begin & SLOT_IX_MASK) | ((my_end & SLOT_IX_MASK) << SLOT_END_SHIFT) | ((my_rule_n & 1u) << SLOT_EO_SHIFT);
         slots.backdrop = my_backdrop;
         // (unpacked by the slot's lane once, read back with one broadcast load per fill: every lane converting the four
@@ -1614,8 +1622,8 @@ __device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t
         uint32_t after = cmd_ix;
         {
             uint32_t sz = 0u;
-            if (win == CMD_FILL && lane <= 60u) sz = 4u;
-            else if (win == CMD_COLOR && lane <= 62u) sz = 2u;
+            if (win == CMD_FILL && lane <= FINE_FILL_LAST_POS) sz = 4u;
+            else if (win == CMD_COLOR && lane <= FINE_COLOR_LAST_POS) sz = 2u;
             uint32_t jump = sz == 0u ? lane : minu(lane + sz, 63u);
             uint32_t pos = 0u;
 #pragma unroll
@@ -1625,7 +1633,7 @@ __device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t
                 jump = wave_shfl(jump, jump);
             }
             const uint32_t tag_k = wave_shfl(win, pos);
-            const bool ok = (lane & 1u) != 0u ? (tag_k == CMD_COLOR && pos <= 62u) : (tag_k == CMD_FILL && pos <= 60u);
+            const bool ok = (lane & 1u) != 0u ? (tag_k == CMD_COLOR && pos <= FINE_COLOR_LAST_POS) : (tag_k == CMD_FILL && pos <= FINE_FILL_LAST_POS);
             const unsigned long long bad = __ballot(!ok);
             pairs = (bad ? (uint32_t)__ffsll((long long)bad) - 1u : 64u) >> 1;
             // (two equal positions in a row -- the chain stuck at a word that is neither -- fail the alternation by themselves:
@@ -1776,7 +1784,7 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
         return (uint32_t)__builtin_amdgcn_readlane((int)win, (int)__builtin_amdgcn_readfirstlane((int)(ix - win_base)));
     };
     auto ensure = [&](uint32_t ix, uint32_t n_words) {
-        if (ix + n_words > win_base + 64u) {
+        if (ix + n_words > win_base + FINE_WINDOW_WORDS) {
             win_base = ix;
             uint32_t a = win_base + lane;
             win = a < cfg.ptcl_size ? ptcl[a] : 0u;
@@ -1846,8 +1854,8 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
                 // look ahead: [COLOR] FILL -> prefetch its first segment batch into registers
                 pre_seg_data = ~0u;
                 uint32_t nx = cmd_ix + 4u;
-                if (nx + 2u <= win_base + 64u && rd(nx) == CMD_COLOR) nx += 2u;
-                if (nx + 4u <= win_base + 64u && rd(nx) == CMD_FILL) {
+                if (nx + 2u <= win_base + FINE_WINDOW_WORDS && rd(nx) == CMD_COLOR) nx += 2u;
+                if (nx + 4u <= win_base + FINE_WINDOW_WORDS && rd(nx) == CMD_FILL) {
                     uint32_t n2 = rd(nx + 1u) >> 1;
                     pre_seg_data = rd(nx + 2u);
                     if (lane < minu(n2, 64u)) pre = segments[pre_seg_data + lane];
@@ -1863,7 +1871,7 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
                     // the scan wants to see as far ahead as possible: a window that starts at (or a draw command in front
                     // of) this command -- the one requested when the previous batch was staged, if the list went on there
                     if (cmd_ix != win_base) {
-                        if (pf_base != 0xffffffffu && cmd_ix >= pf_base && cmd_ix - pf_base <= 8u) {
+                        if (pf_base != 0xffffffffu && cmd_ix >= pf_base && cmd_ix - pf_base <= FINE_PREFETCH_REACH) {
                             win = pf_win;
                             win_base = pf_base;
                         } else {
@@ -1979,7 +1987,7 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
             }
             cmd_ix += 4u;
             // FILL is followed by its draw command, CMD_COLOR as a rule: blend right away instead of going round the loop
-            if (cmd_ix + 2u <= win_base + 64u && rd(cmd_ix) == CMD_COLOR) {
+            if (cmd_ix + 2u <= win_base + FINE_WINDOW_WORDS && rd(cmd_ix) == CMD_COLOR) {
                 const vec4 fg = unpack4x8unorm(rd(cmd_ix + 1u));
 #pragma unroll
                 for (int i = 0; i < 4; i++) src_over(rgba[i], fg, area[i]);
@@ -1996,7 +2004,7 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
 #pragma unroll
             for (int i = 0; i < 4; i++) area[i] = 1.0f;
             cmd_ix += 1u;
-            if (cmd_ix + 2u <= win_base + 64u && rd(cmd_ix) == CMD_COLOR) {  // (as after FILL)
+            if (cmd_ix + 2u <= win_base + FINE_WINDOW_WORDS && rd(cmd_ix) == CMD_COLOR) {  // (as after FILL)
                 const vec4 fg = unpack4x8unorm(rd(cmd_ix + 1u));
 #pragma unroll
                 for (int i = 0; i < 4; i++) src_over(rgba[i], fg, area[i]);
@@ -2123,5 +2131,13 @@ void launch_fine(const Frame &f, hipStream_t s) {
     else if (f.aa == 1) launch_fine_aa<1>(f, s, f.mask_lut8);
     else launch_fine_aa<2>(f, s, f.mask_lut16);
 }
+
+// Test seam (vello_hip_stage_constant)
+uint32_t fine_window_words() { return FINE_WINDOW_WORDS; }
+uint32_t fine_batch_fills() { return MS_BATCH_FILLS; }
+uint32_t fine_batch_segments() { return MS_BATCH_SEGMENTS; }
+uint32_t fine_item_cap() { return MS_ITEM_CAP; }
+uint32_t fine_simple_records() { return MS_SIMPLE_RECORDS; }
+uint32_t fine_prefetch_reach() { return FINE_PREFETCH_REACH; }
 
 }  // namespace vk

@@ -154,6 +154,21 @@ uint32_t vello_hip_stage_constant(int which) {
     case VELLO_HIP_SHAPE_FRONT_MAX_TAGS: return FRONT_MAX_TAGS;
     case VELLO_HIP_SHAPE_FRONT_MAX_DRAW_OBJECTS: return FRONT_MAX_DRAW_OBJECTS;
     case VELLO_HIP_SHAPE_FRONT_TINY_SEGMENTS: return FRONT_TINY_SEGMENTS;
+    case VELLO_HIP_SHAPE_FINE_WINDOW_WORDS: return fine_window_words();
+    case VELLO_HIP_SHAPE_FINE_BATCH_FILLS: return fine_batch_fills();
+    case VELLO_HIP_SHAPE_FINE_BATCH_SEGMENTS: return fine_batch_segments();
+    case VELLO_HIP_SHAPE_FINE_ITEM_CAP: return fine_item_cap();
+    case VELLO_HIP_SHAPE_FINE_SIMPLE_RECORDS: return fine_simple_records();
+    case VELLO_HIP_SHAPE_FINE_PREFETCH_REACH: return fine_prefetch_reach();
+    case VELLO_HIP_SHAPE_FINE_SLICE_FILLS: return FINE_SLICE_FILLS;
+    case VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS: return FINE_SLICE_MIN_FILLS;
+    case VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS_IN_FLIGHT: return FINE_SLICE_MIN_FILLS_IN_FLIGHT;
+    case VELLO_HIP_SHAPE_FINE_SLICE_FILLS_FORCED: return FINE_SLICE_FILLS_FORCED;
+    case VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS_FORCED: return FINE_SLICE_MIN_FILLS_FORCED;
+    case VELLO_HIP_SHAPE_FINE_HEAVY_WORDS: return FINE_HEAVY_WORDS;
+    case VELLO_HIP_SHAPE_FINE_BUCKET_WORDS: return FINE_BUCKET_WORDS;
+    case VELLO_HIP_SHAPE_FINE_BUCKETS: return FINE_WORK_BUCKETS;
+    case VELLO_HIP_SHAPE_PTCL_INITIAL_ALLOC: return PTCL_INITIAL_ALLOC;
     default: return 0u;
     }
 }

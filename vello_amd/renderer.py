@@ -686,7 +686,10 @@ class Engine:
 
     STAGE_CONSTANTS = ("pathtag_part_tags", "flatten_block_tags", "draw_part", "clip_part", "draw_workgroup", "coarse_batch", "coarse_grid_bins",
                        "path_count_chunk", "path_count_chunk_small", "path_count_chunk_in_flight", "path_tiling_workgroup", "backdrop_block_tiles",
-                       "front_max_tags", "front_max_draw_objects", "front_tiny_segments")
+                       "front_max_tags", "front_max_draw_objects", "front_tiny_segments",
+                       "fine_window_words", "fine_batch_fills", "fine_batch_segments", "fine_item_cap", "fine_simple_records", "fine_prefetch_reach",
+                       "fine_slice_fills", "fine_slice_min_fills", "fine_slice_min_fills_in_flight", "fine_slice_fills_forced",
+                       "fine_slice_min_fills_forced", "fine_heavy_words", "fine_bucket_words", "fine_buckets", "ptcl_initial_alloc")
 
     def stage_constants(self):
         """vello_hip_stage_constant: the sizes at which the pipeline's kernels and the host's launch switches cut their work (a test
