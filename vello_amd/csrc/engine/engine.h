@@ -103,7 +103,11 @@ struct Control {
     uint32_t work_count[FINE_WORK_BUCKETS];  // coarse -> fine: tiles per bucket of command-list length (k_fine runs the long ones first)
     uint32_t slice_items;   // coarse -> fine: SliceItems handed out (may run past the capacity: fine clamps); work_count[BUCKETS]
     uint32_t cov_words;     // coarse -> fine: words of the coverage scratch handed out
-    uint32_t pad2[48 - FINE_WORK_BUCKETS - 2];
+    // coarse prep -> coarse: any word nonzero = the scene holds an opaque solid-colour fill (k_coarse then walks its lists back to
+    // front).  One flag in COARSE_OPAQUE_SHARDS words: every wave of k_coarse_prep that sees such a fill says so, and a scene of
+    // 100 000 of them would otherwise send 1 800 atomics to one address (~12 ns each, see arc_count)
+    uint32_t opaque_fills[8];
+    uint32_t pad2[48 - FINE_WORK_BUCKETS - 2 - 8];
     // flatten: arcs the stroke workgroups set aside, counted in FLATTEN_ARC_SHARDS sub-lists (workgroup b appends to shard b mod
     // 64): ONE counter took 2 800 same-address atomics of ~12 ns each in a burst -- 30 us on the road-map scene
     uint32_t arc_count[64];
@@ -113,6 +117,8 @@ static_assert(sizeof(Control) == 512, "Control");
 static_assert(offsetof(Control, slice_items) == offsetof(Control, work_count) + 4u * FINE_WORK_BUCKETS, "Control::slice_items follows work_count");
 static_assert(offsetof(Control, cov_words) == offsetof(Control, slice_items) + 4u, "Control::cov_words follows slice_items");
 constexpr uint32_t FLATTEN_ARC_SHARDS = 64;
+constexpr uint32_t COARSE_OPAQUE_SHARDS = 8;
+static_assert(sizeof(Control::opaque_fills) == 4u * COARSE_OPAQUE_SHARDS, "Control::opaque_fills");
 // Stroke workgroups of a scene of at most n_seg_max segments.  Side by side with the heavy list's workgroups (one frame in flight,
 // k_flatten_main): one per round of 256 stroked lines, up to 4 096.  As a launch of their own (frames in flight,
 // k_flatten_strokes): 512 -- the two a CU holds -- striding over the rounds: four frames in flight +1.9 % on the road map; the same

@@ -1784,7 +1784,9 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
         return (uint32_t)__builtin_amdgcn_readlane((int)win, (int)__builtin_amdgcn_readfirstlane((int)(ix - win_base)));
     };
     auto ensure = [&](uint32_t ix, uint32_t n_words) {
-        if (ix + n_words > win_base + FINE_WINDOW_WORDS) {
+        // (ix < win_base: a CMD_JUMP towards lower addresses -- coarse's back-to-front form links a batch's region to the
+        // regions it allocated before)
+        if (ix + n_words > win_base + FINE_WINDOW_WORDS || ix < win_base) {
             win_base = ix;
             uint32_t a = win_base + lane;
             win = a < cfg.ptcl_size ? ptcl[a] : 0u;
