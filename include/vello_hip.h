@@ -524,6 +524,68 @@ int vello_hip_render_retained_painted(vello_hip_ctx *ctx, const float *transform
                                       void *out_device, size_t out_stride);
 int vello_hip_release_retained(vello_hip_ctx *ctx);
 
+/* Per-frame path data: a frame of the resident scene whose path-data words -- the points themselves -- are a blend of two sources,
+ * without re-encoding and without a byte crossing PCIe per frame: a Lottie-style shape morph (keyframes share one tag stream by
+ * construction), the edges of a graph whose node positions a GPU op computes, curves a simulation leaves in a device tensor.  The
+ * reference has no such input (Scene::reset and encode again); like views, poses and paints this extends the boundary, and the
+ * contract is stated here.  vello_hip_render_resident is unchanged: the same kernels, the same bytes.
+ *   1. SOURCES.  src_a and src_b are each a keyframe index below the n_keys of vello_hip_upload_path_keyframes,
+ *      VELLO_HIP_PATH_DATA_SCENE (the resident scene's own stream) or VELLO_HIP_PATH_DATA_DEVICE (`device_words`).  A source is
+ *      N = vello_hip_path_data_words(ctx) words long (draw_tag_base - path_data_base of the resident scene; 0 when none is
+ *      resident).  `device_words`: N words, 4-byte aligned -- a tensor slice that starts one float in is legal -- in one
+ *      allocation on the context's device (anything else is refused in GPU builds, as device poses are refused).  The host never
+ *      reads it.
+ *   2. THE FRAME'S WORDS W, for every word i < N.  W[i] = A[i] verbatim (a bit copy: NaN payloads and signed zeros included) when
+ *      src_a == src_b or t == 0.0f (either sign); W[i] = B[i] verbatim when t == 1.0f; otherwise
+ *          W[i] = fl(A[i] + fl(t * fl(B[i] - A[i])))
+ *      in f32, each of the three operations rounded on its own (no contraction into an FMA).  Any finite t is legal: t outside
+ *      [0, 1] extrapolates.  A NaN result has an unspecified payload.  "Points from a device tensor" is
+ *      src_a == src_b == VELLO_HIP_PATH_DATA_DEVICE.
+ *   3. WHAT A MORPHED FRAME IS.  Bit for bit in every buffer and counter, the frame vello_hip_render_resident would enqueue had
+ *      the scene been uploaded with W in the place of its path-data stream (the line soup and the segment slices as multisets, as
+ *      everywhere) -- under a view transform and viewport culling, both applied to the morphed geometry; with frames in flight;
+ *      with the scene index and without it; in the small-scene launches and without them; with every kernel choice of the
+ *      debug flags.  ONE kernel (k_path_blend, a streaming pass: two reads and a write per word, one read in the verbatim cases)
+ *      writes W into a per-buffer-set copy of the stream behind the scene's bytes at the head of the frame; the kernels that read
+ *      path data are handed the copy in the stream's place.  Nothing in the scene index depends on a point, so it stays valid and
+ *      no frame builds one.  VELLO_HIP_BUF_SCENE shows the uploaded bytes, VELLO_HIP_BUF_CONFIG the scene's own layout.
+ *      vello_hip_run_stages after a morphed frame goes on from that frame's words as they are (the sources are not read again).
+ *      vello_hip_pick and vello_hip_pick_rect answer against the morphed geometry: they read the frame's soup.
+ *   4. BLENDS NEED FLOATS.  The third case of rule 2 is refused with VELLO_HIP_E_INVALID on a scene that holds an i16 segment
+ *      tag (tag & 3 != 0 and tag & 8 == 0; found once, when the scene is uploaded): its words are pairs of 16-bit integers.
+ *      Verbatim frames are legal on any scene.
+ *   5. KEYFRAMES.  vello_hip_upload_path_keyframes copies n_keys alternative path-data streams (host memory, n_words words each,
+ *      keyframe k at words + k * n_words) into a device buffer the context owns (vello_hip_destroy frees it).  It waits for the
+ *      frames in flight, as an upload does; a second call replaces the set, n_keys == 0 drops it, and every upload of a scene
+ *      (vello_hip_upload_scene, vello_hip_render's own, vello_hip_upload_fragments) drops it.  VELLO_HIP_E_INVALID with nothing
+ *      changed: no resident scene, n_words != vello_hip_path_data_words(ctx), words == NULL with n_keys > 0.  Keyframe contents
+ *      are not validated, as a scene's own points are not.
+ *   6. ORDERING.  With `src_stream` (a hipStream_t; legal only when a source is VELLO_HIP_PATH_DATA_DEVICE) the frame waits for
+ *      what has been enqueued on it so far, and src_stream then waits for k_path_blend: work enqueued there afterwards may
+ *      overwrite device_words -- the kernel has copied what the frame needs.  Nothing waits on the host.  Without src_stream the
+ *      caller keeps device_words unchanged until the frame has finished.
+ *   7. REFUSALS.  VELLO_HIP_E_INVALID, vello_hip_last_error naming the rule, nothing enqueued and the rotation of the in-flight
+ *      buffer sets where it was: a null context; no resident scene; a source index >= n_keys; VELLO_HIP_PATH_DATA_DEVICE with a
+ *      null, misaligned or non-device device_words; device_words or src_stream given although no source names the device; a NaN
+ *      or infinite t; rule 4; every refusal of vello_hip_render_resident (target, parameters); a scene whose bytes and copies
+ *      together would reach 2^32 words (the copy must be reachable with the scene pointer and a u32 word offset).
+ *   8. W BELONGS TO ITS FRAME.  Four frames in flight may show four values of t, or four device tensors, in four targets.  A
+ *      vello_hip_render_resident frame that follows a morphed one on the same buffer set shows the scene's own points.  No frame
+ *      modifies the resident bytes or the keyframes.  The room for the copies is made at most once per resident scene, by
+ *      vello_hip_upload_path_keyframes or by the first morphed frame: that may re-allocate the scene buffer, which waits for the
+ *      frames in flight and counts in vello_hip_scene_allocations.  A steady state of morphed frames allocates nothing.
+ *   9. Out of scope: morphing private scenes (vello_hip_render_frame), composed instance frames and the retained list; keyframes
+ *      whose tag streams differ; easing curves, or more than two sources per frame; host-memory sources per frame (a host uploads
+ *      keyframes); pool estimation for morphed frames -- an overflow is reported at vello_hip_sync as always, and
+ *      vello_hip_grow_pools plus a second call render the frame again. */
+#define VELLO_HIP_PATH_DATA_SCENE 0xFFFFFFFFu  /* the resident scene's own path-data stream */
+#define VELLO_HIP_PATH_DATA_DEVICE 0xFFFFFFFEu /* the caller's device memory (device_words) */
+uint32_t vello_hip_path_data_words(vello_hip_ctx *ctx);
+int vello_hip_upload_path_keyframes(vello_hip_ctx *ctx, const uint32_t *words, uint32_t n_keys, uint32_t n_words);
+int vello_hip_render_resident_morphed(vello_hip_ctx *ctx, uint32_t src_a, uint32_t src_b, float t,
+                                      const uint32_t *device_words /* nullable */, void *src_stream /* nullable hipStream_t */,
+                                      const vello_hip_render_params *params, void *out_device, size_t out_stride);
+
 /* Hit testing: the topmost draw object, and the instance that owns it, under each of n points of the frame submitted last on the
  * context -- the frame whose buffers vello_hip_read_buffer shows.  The reference has no hit test; like instances and views this
  * extends the boundary, and the contract is stated here.  Everything is read from what the frame left on the device (the line soup,
@@ -647,7 +709,8 @@ int vello_hip_pick_rect(vello_hip_ctx *ctx, const float rect[4] /* x0 y0 x1 y1, 
  * most records of a fill that takes the straight-line replay; how many words behind a prefetched window's base the list may resume
  * for the window to be used; the fills per slice of a long tile and the fills from which a tile is sliced (one frame in flight,
  * frames in flight; both under VELLO_HIP_DEBUG_FINE_SLICES); the command words from which a tile counts as heavy; the words per
- * bucket and the buckets of fine's tile order; the words of a tile's fixed command block.  0 for any other `which`. */
+ * bucket and the buckets of fine's tile order; the words of a tile's fixed command block; the words a workgroup of k_path_blend
+ * takes per grid step in its 16-byte form.  0 for any other `which`. */
 enum { VELLO_HIP_SHAPE_PATHTAG_PART_TAGS = 0, VELLO_HIP_SHAPE_FLATTEN_BLOCK_TAGS = 1, VELLO_HIP_SHAPE_DRAW_PART = 2, VELLO_HIP_SHAPE_CLIP_PART = 3,
        VELLO_HIP_SHAPE_DRAW_WORKGROUP = 4, VELLO_HIP_SHAPE_COARSE_BATCH = 5, VELLO_HIP_SHAPE_COARSE_GRID_BINS = 6,
        VELLO_HIP_SHAPE_PATH_COUNT_CHUNK = 7, VELLO_HIP_SHAPE_PATH_COUNT_CHUNK_SMALL = 8, VELLO_HIP_SHAPE_PATH_COUNT_CHUNK_IN_FLIGHT = 9,
@@ -657,7 +720,9 @@ enum { VELLO_HIP_SHAPE_PATHTAG_PART_TAGS = 0, VELLO_HIP_SHAPE_FLATTEN_BLOCK_TAGS
        VELLO_HIP_SHAPE_FINE_ITEM_CAP = 18, VELLO_HIP_SHAPE_FINE_SIMPLE_RECORDS = 19, VELLO_HIP_SHAPE_FINE_PREFETCH_REACH = 20,
        VELLO_HIP_SHAPE_FINE_SLICE_FILLS = 21, VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS = 22, VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS_IN_FLIGHT = 23,
        VELLO_HIP_SHAPE_FINE_SLICE_FILLS_FORCED = 24, VELLO_HIP_SHAPE_FINE_SLICE_MIN_FILLS_FORCED = 25, VELLO_HIP_SHAPE_FINE_HEAVY_WORDS = 26,
-       VELLO_HIP_SHAPE_FINE_BUCKET_WORDS = 27, VELLO_HIP_SHAPE_FINE_BUCKETS = 28, VELLO_HIP_SHAPE_PTCL_INITIAL_ALLOC = 29, VELLO_HIP_SHAPE_COUNT = 30 };
+       VELLO_HIP_SHAPE_FINE_BUCKET_WORDS = 27, VELLO_HIP_SHAPE_FINE_BUCKETS = 28, VELLO_HIP_SHAPE_PTCL_INITIAL_ALLOC = 29,
+       VELLO_HIP_SHAPE_PATH_BLEND_VEC_WORDS = 30, /* words a workgroup of k_path_blend takes per grid step in its 16-byte form */
+       VELLO_HIP_SHAPE_COUNT = 31 };
 uint32_t vello_hip_stage_constant(int which);
 
 /* Test-seam switches (default 0).  VELLO_HIP_DEBUG_NO_CULL turns off coarse's occlusion culling (a draw hidden under a

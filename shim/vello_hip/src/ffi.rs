@@ -130,6 +130,9 @@ pub const VELLO_HIP_PICK_SMALL_BATCH: c_int = 2;
 pub const VELLO_HIP_PICK_SCRATCH_BYTES: c_int = 3;
 pub const VELLO_HIP_PICK_RECT_LINES_PER_WORKGROUP: c_int = 4;
 pub const VELLO_HIP_PICK_RECT_DRAWS_PER_WORKGROUP: c_int = 5;
+/// The header's `#define`s of the same names: the two sources of `vello_hip_render_resident_morphed` that are not keyframe indices.
+pub const VELLO_HIP_PATH_DATA_SCENE: u32 = 0xFFFF_FFFF;
+pub const VELLO_HIP_PATH_DATA_DEVICE: u32 = 0xFFFF_FFFE;
 pub const VELLO_HIP_PAINT_KEEP: u32 = 0;
 pub const VELLO_HIP_PAINT_SOLID: u32 = 1;
 pub const VELLO_HIP_AA_AREA: u32 = 0;
@@ -171,6 +174,9 @@ unsafe extern "C" {
     pub fn vello_hip_render_retained(ctx: *mut vello_hip_ctx, transforms: *const f32, transforms_is_device: c_int, src_stream: *mut c_void, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_render_retained_painted(ctx: *mut vello_hip_ctx, transforms: *const f32, transforms_is_device: c_int, paints: *const vello_hip_paint, paints_is_device: c_int, src_stream: *mut c_void, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_release_retained(ctx: *mut vello_hip_ctx) -> c_int;
+    pub fn vello_hip_path_data_words(ctx: *mut vello_hip_ctx) -> u32;
+    pub fn vello_hip_upload_path_keyframes(ctx: *mut vello_hip_ctx, words: *const u32, n_keys: u32, n_words: u32) -> c_int;
+    pub fn vello_hip_render_resident_morphed(ctx: *mut vello_hip_ctx, src_a: u32, src_b: u32, t: f32, device_words: *const u32, src_stream: *mut c_void, params: *const vello_hip_render_params, out_device: *mut c_void, out_stride: usize) -> c_int;
     pub fn vello_hip_pick(ctx: *mut vello_hip_ctx, points: *const f32, n: u32, points_is_device: c_int, src_stream: *mut c_void, out: *mut vello_hip_pick_hit, out_is_device: c_int) -> c_int;
     pub fn vello_hip_pick_ms(ctx: *mut vello_hip_ctx, ms_out: *mut f32) -> c_int;
     pub fn vello_hip_pick_constant(which: c_int) -> u32;

@@ -12,11 +12,12 @@ from .kurbo import Affine, BezPath, Circle, Rect, RoundedRect, Line, Stroke, Joi
 from .scene import (Scene, Fill, Color, BlendMode, Mix, Compose, Gradient, Extend, InterpolationAlphaSpace, ImageData, ImageBrush,
                     ImageFormat, ImageAlphaType, ImageQuality, Resolver, Resolved)
 from .renderer import (Renderer, RenderParams, AaConfig, RendererOptions, Engine, Layout, FragmentLibrary, INSTANCE_DTYPE, PAINT_DTYPE, PICK_NONE, REGION_TOUCHED, REGION_ENCLOSED,
-                       paint_array)
+                       paint_array, PATH_DATA_SCENE, PATH_DATA_DEVICE, path_data_view)
 
 __all__ = [
     "load_library", "library_path", "VelloHipError", "Affine", "BezPath", "Circle", "Rect", "RoundedRect", "Line",
     "Stroke", "Join", "Cap", "Scene", "Fill", "Color", "BlendMode", "Mix", "Compose", "Renderer", "RenderParams",
     "AaConfig", "RendererOptions", "Engine", "Layout", "Gradient", "Extend", "InterpolationAlphaSpace", "ImageData", "ImageBrush",
     "ImageFormat", "ImageAlphaType", "ImageQuality", "Resolver", "Resolved", "FragmentLibrary", "INSTANCE_DTYPE", "PAINT_DTYPE", "PICK_NONE", "REGION_TOUCHED", "REGION_ENCLOSED", "paint_array",
+    "PATH_DATA_SCENE", "PATH_DATA_DEVICE", "path_data_view",
 ]

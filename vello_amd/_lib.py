@@ -119,6 +119,9 @@ def load_library():
     sig("vello_hip_render_retained", i32, [vp, vp, i32, vp, c.POINTER(RenderParamsStruct), vp, sz])
     sig("vello_hip_render_retained_painted", i32, [vp, vp, i32, vp, i32, vp, c.POINTER(RenderParamsStruct), vp, sz])
     sig("vello_hip_release_retained", i32, [vp])
+    sig("vello_hip_path_data_words", u32, [vp])
+    sig("vello_hip_upload_path_keyframes", i32, [vp, vp, u32, u32])
+    sig("vello_hip_render_resident_morphed", i32, [vp, u32, u32, c.c_float, vp, vp, c.POINTER(RenderParamsStruct), vp, sz])
     sig("vello_hip_pick", i32, [vp, vp, u32, i32, vp, vp, i32])
     sig("vello_hip_pick_constant", u32, [i32])
     sig("vello_hip_pick_rect_sizes", i32, [vp, c.POINTER(u32), c.POINTER(u32)])

@@ -75,7 +75,18 @@ struct SceneSlot {
     // (every other slot; a list so large that the copies would be out of a u32 word offset's reach -- it takes no paints).
     size_t dd_at = 0;
     uint32_t dd_sets = 0, dd_set_words = 0;
+    // The shared slot only: the path-data words of MORPHED frames (vello_hip_render_resident_morphed, Frame::pd_base) -- `pd_sets`
+    // copies (a lane each) of `pd_set_words` words from word `pd_at` of the scene's allocation: behind the transform copies, in the
+    // same tail (view_cap_bytes covers both).  A copy is the stream's length plus PD_SLACK_WORDS, rounded up to whole quads, and
+    // begins on a 16-byte boundary; its slack holds the words that follow the stream in the scene, so that a read behind the
+    // stream's end (flatten's look at the tag after a stroked segment) finds what it finds in the scene itself.  pd_sets == 0: no
+    // room yet -- it is made once per resident scene, by vello_hip_upload_path_keyframes or the first morphed frame
+    // (ensure_morph_room), not by the upload: scenes that are never morphed pay nothing.
+    size_t pd_at = 0;
+    uint32_t pd_sets = 0, pd_set_words = 0;
+    bool i16_segments = false;  // a segment tag without PATH_TAG_F32 is present (found by load_slot from the host bytes): no blends
 };
+constexpr uint32_t PD_SLACK_WORDS = 8u;  // (a cubic's four points: what read_path_segment reads from a tag's offset on)
 // A fragment of the library as the host keeps it: where its range begins in each stream and how long it is -- in the units of
 // ComposeArgs (bytes for tags, words otherwise) -- what the composed layout and fine's specialisation need of its draw tags, and
 // where the mask of its colour words lies (vello_hip_render_instances_painted).
@@ -127,7 +138,17 @@ struct Lane {
     // ctx::retained.generation of the list whose painted draw-data words the lane's copy holds BECAUSE the lane's latest retained
     // frame was a painted one (0: it was not): vello_hip_run_stages after a painted frame goes on from them
     uint64_t painted_generation = 0;
-    DevBuf front_sync;                // k_front's grid-barrier counter (zeroed once, when allocated)
+    // vello_hip_render_resident_morphed: where the frame's k_path_blend reads its two sources (the shared scene's stream, the
+    // context's keyframes or the caller's device memory; pd_a null: not a morphed frame), its mode and t, and the caller's stream
+    // that waits for it (null: none).  They belong to the frame being entered and are cleared before the entry point returns.
+    const uint32_t *pd_a = nullptr, *pd_b = nullptr;
+    uint32_t pd_mode = 0;
+    float pd_t = 0.0f;
+    hipStream_t pd_stream = nullptr;
+    // ctx::shared.generation of the scene whose morphed path-data words the lane's copy holds BECAUSE the lane's latest frame of the
+    // shared scene was a morphed one (0: it was not): vello_hip_run_stages after a morphed frame goes on from them
+    uint64_t morphed_generation = 0;
+    DevBuf front_sync;               // k_front's grid-barrier counter (zeroed once, when allocated)
     uint32_t front_sync_value = 0;    // ... and its value once every launch enqueued so far has run
     struct EvPair {
         int stage;
@@ -176,6 +197,11 @@ struct vello_hip_ctx {
     vk::DevBuf config;
     vk::DevBuf mask8, mask16;
     vk::SceneSlot shared;  // vello_hip_upload_scene: one scene for every lane
+    // vello_hip_upload_path_keyframes: n_keys alternative path-data streams of the shared scene, keyframe k at word
+    // k * key_stride -- the stream's length rounded up to whole quads: every keyframe is 16-byte aligned (dropped by every upload
+    // into the shared slot; the buffer stays for the next set)
+    vk::DevBuf keyframes;
+    uint32_t n_keys = 0, key_stride = 0;
     // vello_hip_upload_fragments: the shared scene as a library of fragments (dropped by the next vello_hip_upload_scene)
     std::vector<vk::FragmentInfo> fragments;
     bool have_fragments = false;
@@ -277,12 +303,14 @@ int alloc_lane_scene(vello_hip_ctx *c, Lane &l, const SceneSlot &sc);
 int check_target(vello_hip_ctx *c, const vello_hip_render_params *p, const void *out, size_t out_stride, bool device);
 int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
 int paint_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
+int morph_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
 int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, void *out_device, size_t out_stride, Frame &f, bool upload_cfg);
 int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int last);
 // scenes.hip
 int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
               const uint32_t *ramps, uint32_t n_ramps);
 void drop_retained(vello_hip_ctx *c);
+int ensure_morph_room(vello_hip_ctx *c);
 // atlas.hip
 int acquire_staging(vello_hip_ctx *c, size_t bytes, Staging *&out);
 // seams.hip

@@ -183,6 +183,19 @@ struct Frame {
     const uint32_t *dd_map;
     const uint32_t *paint_words;
     bool paint_check;
+    // The path-data words flatten reads: scene[(u32)(pd_base + offset)].  The scene's own stream (pd_base == cfg.layout.path_data_base)
+    // for every frame but a MORPHED frame of the resident scene (vello_hip_render_resident_morphed): there it is the lane's copy of
+    // the stream behind the scene's bytes and the transform copies, which k_path_blend fills at the head of the frame from two
+    // sources (pd_a, pd_b: the scene's stream, a resident keyframe or the caller's device memory; pd_a null: the copy already holds
+    // the frame's words, nothing is launched -- vello_hip_run_stages after a morphed frame).  pd_mode / pd_t: PathBlendArgs.
+    // pd_stream (nullable) is the caller's stream that waits for that kernel, through pose_mark.  The readers are handed a Config
+    // whose layout.path_data_base is pd_base (xf_config) and are the same code whether the frame is morphed or not.  The pathtag
+    // scan keeps the scene's own Config: it judges lengths against the scene's layout.
+    uint32_t pd_base;
+    const uint32_t *pd_a, *pd_b;
+    uint32_t pd_mode;
+    float pd_t;
+    hipStream_t pd_stream;
     Control *control;
     uint32_t *heavy_list;   // flatten: tag indices that need the Euler-spiral / stroker path
     uint32_t *arc_items;    // flatten: 16 words per round join / cap arc that a stroke workgroup leaves to the heavy code
@@ -243,13 +256,17 @@ struct Frame {
 };
 
 // the Config of the kernels that read transforms (flatten's, the draw stage's): the frame's, with the transform words' base -- and
-// the draw-data words' base, which the draw stage reads through the same Config (an unpainted frame's: the scene's own)
+// the draw-data words' base, which the draw stage reads through the same Config (an unpainted frame's: the scene's own), and the
+// path-data words' base, which flatten reads through it (an unmorphed frame's: the scene's own)
 inline Config xf_config(const Frame &f) {
     Config c = f.cfg;
     c.layout.transform_base = f.xf_base;
     c.layout.draw_data_base = f.dd_base;
+    c.layout.path_data_base = f.pd_base;
     return c;
 }
+// whether the frame's path-data words are the lane's copy (a morphed frame, or vello_hip_run_stages after one)
+inline bool morphed(const Frame &f) { return f.pd_base != f.cfg.layout.path_data_base; }
 // the Config of k_coarse_prep, which reads draw data and no transforms: the frame's, with the draw-data words' base
 inline Config dd_config(const Frame &f) {
     Config c = f.cfg;
@@ -290,6 +307,22 @@ struct InstancePaintArgs {
 // fills the draw-data words of a painted retained frame (Frame::paint_words is set); check_paints: the frame's control block has
 // been cleared on `s` and the pathtag scan has not been enqueued yet
 void launch_instance_paints(const Frame &f, bool check_paints, hipStream_t s);
+// k_path_blend (scene_ops.hip): what it is handed by value.  Word i of `out` is a[i] (PATH_BLEND_COPY_A), b[i] (PATH_BLEND_COPY_B) or
+// fl(a[i] + fl(t * fl(b[i] - a[i]))) (PATH_BLEND_MIX): rule 2 of vello_hip_render_resident_morphed.  The host picks the mode -- the
+// verbatim cases read ONE stream -- and the access width: 16-byte accesses when every address the mode touches is 16-byte aligned,
+// dword accesses otherwise (launch_path_blend).
+//   PATH_BLEND_VEC_WORDS  words a workgroup takes per grid step in the 16-byte form (256 lanes x 4 words)
+constexpr uint32_t PATH_BLEND_COPY_A = 0u, PATH_BLEND_COPY_B = 1u, PATH_BLEND_MIX = 2u;
+constexpr uint32_t PATH_BLEND_VEC_WORDS = 1024u, PATH_BLEND_MAX_WGS = 2048u;
+struct PathBlendArgs {
+    const uint32_t *a, *b;  // the two sources, n words each, 4-byte aligned (the one a copy mode does not name is not read)
+    uint32_t *out;          // word 0 of the lane's copy
+    uint32_t n;
+    uint32_t mode;          // PATH_BLEND_*
+    float t;
+};
+// fills the path-data words of a morphed frame (Frame::pd_a is set)
+void launch_path_blend(const Frame &f, hipStream_t s);
 
 void launch_pathtag_scan(const Frame &f, hipStream_t s);
 // k_frame_begin (scan.hip), an indexed frame's first launch: the zero fill of the lane's zero region, the path boxes from the

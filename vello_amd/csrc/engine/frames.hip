@@ -145,6 +145,19 @@ int paint_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &b
     return 0;
 }
 
+// Where lane l's copy of the shared scene's path-data words lies, in words from the scene's start (SceneSlot::pd_at): what a morphed
+// frame reads in the stream's place.  VELLO_HIP_E_INVALID while the slot has no room for the copies (ensure_morph_room makes it).
+int morph_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base) {
+    const size_t set = (size_t)(&l - c->lanes.data());
+    const uint64_t at = (uint64_t)sc.pd_at + (uint64_t)set * sc.pd_set_words;
+    if (set >= sc.pd_sets || at + sc.pd_set_words > 0xffffffffull) {
+        c->last_error = "the scene has no room for per-frame path data (its bytes and copies must lie within 2^32 words of its start)";
+        return VELLO_HIP_E_INVALID;
+    }
+    base = (uint32_t)at;
+    return 0;
+}
+
 // The target contract of include/vello_hip.h (at vello_hip_render_resident).  fine stores dwords at output + y * stride and takes the
 // stride as a u32: a device target that is not 4-aligned, rows that overlap or a stride of 2^32 and more would corrupt silently.
 // Every entry point that takes a target asks before it uploads, rotates or enqueues anything.
@@ -242,6 +255,21 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
         f.dd_map = (const uint32_t *)c->retained_ddmap.ptr;
         f.paint_words = l.paint_src;
         f.paint_check = l.paint_src && l.paint_check;
+    }
+    // its path-data words: the scene's own -- or, a morphed frame's (the entry point has set the lane's sources) and a
+    // vello_hip_run_stages' after one (the lane's copy holds that frame's words), the lane's copy
+    f.pd_base = sc.layout.path_data_base;
+    f.pd_a = f.pd_b = nullptr;
+    f.pd_mode = PATH_BLEND_COPY_A;
+    f.pd_t = 0.0f;
+    f.pd_stream = nullptr;
+    if (&sc == &c->shared && (l.pd_a || (l.morphed_generation == sc.generation && sc.pd_sets != 0u))) {
+        if ((r = morph_base(c, sc, l, f.pd_base))) return r;
+        f.pd_a = l.pd_a;
+        f.pd_b = l.pd_b;
+        f.pd_mode = l.pd_mode;
+        f.pd_t = l.pd_t;
+        f.pd_stream = l.pd_stream;
     }
     f.control = (Control *)l.zero_region.ptr;
     f.zero_bytes = (uint32_t)sc.zero_bytes;
@@ -405,6 +433,16 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
             HIP_TRY(c, hipStreamWaitEvent(f.pose_stream, f.pose_mark, 0));
         }
     }
+    // A morphed frame: its path-data words first, beside the view's transform words, when the range holds the stage that reads them;
+    // the caller's stream may overwrite its device source once the kernel has read it
+    if (f.pd_a && first <= VELLO_HIP_STAGE_FLATTEN && last >= VELLO_HIP_STAGE_FLATTEN) {
+        launch_path_blend(f, st);
+        HIP_TRY(c, hipGetLastError());
+        if (f.pd_stream) {
+            HIP_TRY(c, hipEventRecord(f.pose_mark, st));
+            HIP_TRY(c, hipStreamWaitEvent(f.pd_stream, f.pose_mark, 0));
+        }
+    }
     const uint32_t front_zero = zeroed ? 0u : FRONT_ZERO;
     for (int s = first; s <= last; s++) {
         bool prof = ((c->prof_mask >> s) & 1u) != 0u;
@@ -525,7 +563,100 @@ int vello_hip_render_resident(vello_hip_ctx *c, const vello_hip_render_params *p
     };
     int last = VELLO_HIP_STAGE_FINE;
     if (const uint32_t ls = (c->debug_flags >> VELLO_HIP_DEBUG_LAST_STAGE_SHIFT) & 15u) last = (int)ls - 1 < last ? (int)ls - 1 : last;  // (measurement seam)
-    return enter_frame(c, params, out_device, out_stride, true, last, set_up, no_step, no_step);
+    // (the lane's copy of the path-data words, if a morphed frame left one, is not this frame's: it shows the scene's own points)
+    Lane &lane = c->lanes[c->next_lane % c->n_active];
+    const uint64_t morphed_was = lane.morphed_generation;
+    lane.morphed_generation = 0u;
+    const int r = enter_frame(c, params, out_device, out_stride, true, last, set_up, no_step, no_step);
+    if (r) lane.morphed_generation = morphed_was;  // (refused: the lane's latest frame is still the one before)
+    return r;
+}
+
+// A frame of the resident scene whose path-data words are blend(A, B, t).  Everything that can refuse the frame is asked before the
+// lane is taken; what the host does per frame does not depend on the scene's size.  The blend's case (rule 2 of the contract) is
+// picked here: the kernel is told to copy one stream or to mix two.
+int vello_hip_render_resident_morphed(vello_hip_ctx *c, uint32_t src_a, uint32_t src_b, float t, const uint32_t *device_words, void *src_stream,
+                                      const vello_hip_render_params *params, void *out_device, size_t out_stride) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    auto refuse = [&](const std::string &why) {
+        c->last_error = "render_resident_morphed: " + why;
+        return VELLO_HIP_E_INVALID;
+    };
+    if (!params) return refuse("params is NULL");
+    if (!c->shared.resident) return refuse("no scene uploaded");
+    const SceneSlot &sc = c->shared;
+    const uint32_t n = sc.layout.draw_tag_base - sc.layout.path_data_base;
+    bool names_device = false;
+    for (const uint32_t src : {src_a, src_b}) {
+        if (src == VELLO_HIP_PATH_DATA_DEVICE) names_device = true;
+        else if (src != VELLO_HIP_PATH_DATA_SCENE && src >= c->n_keys)
+            return refuse("source " + std::to_string(src) + " of " + std::to_string(c->n_keys) + " keyframes (vello_hip_upload_path_keyframes)");
+    }
+    if (!names_device && device_words) return refuse("device_words goes with a VELLO_HIP_PATH_DATA_DEVICE source");
+    if (!names_device && src_stream) return refuse("src_stream goes with a VELLO_HIP_PATH_DATA_DEVICE source");
+    if (!(t - t == 0.0f)) return refuse("t is not finite");
+    if (names_device) {
+        if (!device_words) return refuse("VELLO_HIP_PATH_DATA_DEVICE without device_words");
+        if ((reinterpret_cast<uintptr_t>(device_words) & 3u) != 0u) return refuse("the address of device_words is not a multiple of 4");
+        if (n != 0u)
+            if (const char *why = not_device_memory(c, device_words, (size_t)n * 4u)) return refuse(std::string("device_words ") + why);
+    }
+    const uint32_t mode = src_a == src_b || t == 0.0f ? PATH_BLEND_COPY_A : t == 1.0f ? PATH_BLEND_COPY_B : PATH_BLEND_MIX;
+    if (mode == PATH_BLEND_MIX && sc.i16_segments)
+        return refuse("the scene holds an i16 segment tag: its path data cannot be blended as floats (t = 0, t = 1 and equal sources are legal)");
+    int r;
+    if ((r = check_target(c, params, out_device, out_stride, true))) return r;
+    {
+        Config probe;  // (what prepare_frame would refuse, asked before anything changes)
+        if ((r = configure(c, sc, params, probe))) return r;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the room for the lanes' copies: made once per resident scene (here, unless the keyframes' upload has made it)
+    if ((r = ensure_morph_room(c))) return r;
+    Lane &lane = c->lanes[c->next_lane % c->n_active];  // (the lane enter_frame takes)
+    {
+        uint32_t probe;
+        if ((r = morph_base(c, sc, lane, probe))) return r;
+    }
+    if (src_stream && !c->pose_mark) HIP_TRY(c, hipEventCreateWithFlags(&c->pose_mark, hipEventDisableTiming));
+    const auto source = [&](uint32_t src) -> const uint32_t * {
+        if (src == VELLO_HIP_PATH_DATA_DEVICE) return device_words;
+        if (src == VELLO_HIP_PATH_DATA_SCENE) return (const uint32_t *)sc.scene.ptr + sc.layout.path_data_base;
+        return (const uint32_t *)c->keyframes.ptr + (size_t)src * c->key_stride;
+    };
+    const uint64_t morphed_was = lane.morphed_generation;
+    const auto set_up = [&](Lane &l, bool &new_scene) -> int {
+        new_scene = l.which != LaneScene::Shared;
+        if (!new_scene) return 0;
+        HIP_TRY(c, hipStreamSynchronize(l.stream));
+        l.which = LaneScene::Shared;
+        return 0;
+    };
+    const auto staged = [&](Lane &l) -> int {
+        l.pd_a = source(src_a);
+        l.pd_b = source(src_b);
+        l.pd_mode = mode;
+        l.pd_t = t;
+        l.pd_stream = (hipStream_t)src_stream;
+        l.morphed_generation = sc.generation;
+        return 0;
+    };
+    bool entered = false;
+    const auto enqueue = [&](Lane &l) -> int {
+        entered = true;
+        c->cfg_unsent = true;  // (VELLO_HIP_BUF_CONFIG gets the Config -- the scene's own layout -- when it is next read or written)
+        if (src_stream) {  // behind what the caller's stream has been given so far
+            HIP_TRY(c, hipEventRecord(c->pose_mark, (hipStream_t)src_stream));
+            HIP_TRY(c, hipStreamWaitEvent(l.stream, c->pose_mark, 0));
+        }
+        return 0;
+    };
+    r = enter_frame(c, params, out_device, out_stride, false, VELLO_HIP_STAGE_FINE, set_up, staged, enqueue);
+    // the sources belonged to this frame, enqueued or refused: the lane keeps neither the caller's memory nor the caller's stream
+    lane.pd_a = lane.pd_b = nullptr;
+    lane.pd_stream = nullptr;
+    if (!entered) lane.morphed_generation = morphed_was;  // (refused: the lane's latest frame is still the one before)
+    return r;
 }
 
 // A frame of the retained instance list under this frame's poses and paints.  Everything that can refuse the frame is asked before
@@ -675,6 +806,8 @@ int vello_hip_run_stages(vello_hip_ctx *c, const vello_hip_render_params *params
         f.pose_check = false;
         f.pose_words = l.posed_generation == c->retained.generation ? nullptr : (const uint32_t *)c->retained_rest.ptr;
     }
+    // (after a morphed frame: prepare_frame has picked the lane's copy of the path-data words, which holds that frame's words -- no
+    // source is set on the lane outside vello_hip_render_resident_morphed, so nothing is blended again)
     if ((r = run_stage_range(c, l, f, first, last))) return r;
     HIP_TRY(c, hipStreamSynchronize(l.stream));
     return VELLO_HIP_OK;

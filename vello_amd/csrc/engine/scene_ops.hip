@@ -1,5 +1,5 @@
 // Device-side operations on scene data outside the pipeline's stages: atlas copies, the view's transform words, a retained list's
-// per-frame transform and draw-data words, scene composition.
+// per-frame transform and draw-data words, a morphed frame's path-data words, scene composition.
 #include "engine.h"
 
 namespace vk {
@@ -201,6 +201,76 @@ void launch_instance_paints(const Frame &f, bool check_paints, hipStream_t s) {
     const uint32_t lanes = a.n_words > (check_paints ? a.n : 0u) ? a.n_words : (check_paints ? a.n : 0u);
     if (lanes == 0u) return;  // (no draw data and nothing to test)
     hipLaunchKernelGGL(k_instance_paints, dim3((lanes + 255u) / 256u), dim3(256), 0, s, a);
+}
+
+// k_path_blend: the path-data words of a MORPHED frame of the resident scene (vello_hip_render_resident_morphed; the arguments are in
+// engine.h), beside k_view_transforms at the head of the frame.  Word i of `out` -- the lane's copy of the stream, which flatten then
+// reads in the stream's place -- is a[i], b[i] or a[i] + t * (b[i] - a[i]): f32, the difference, the product and the sum each rounded
+// on its own (the tree is built without fp contraction, as k_view_transforms' arithmetic is), in this operand order.  The copy modes
+// move bits: a NaN's payload and a zero's sign arrive as they were.  A plain streaming pass -- two reads and a write per word, one read
+// in the copy modes; no LDS, nothing is shared -- over a grid capped at PATH_BLEND_MAX_WGS workgroups (eight per CU) that strides
+// over the rest.  VEC: every address the mode touches is 16-byte aligned (the host has looked): lane l of a step takes the four words
+// of one dwordx4 access, a wave 1 KB of consecutive memory per stream, and the up to three words behind the last whole quad are
+// lanes 0 .. 2 of workgroup 0 with dword accesses.  !VEC (a keyframe whose length is no multiple of four, a tensor slice that starts
+// one float in): a word a lane, 256 B a wave.  The mode is wave-uniform: a kernel argument.
+__device__ __forceinline__ uint32_t path_blend_word(uint32_t a, uint32_t b, float t) {
+    // __fsub_rn / __fmul_rn / __fadd_rn of the contract: in this toolchain they ARE the plain operators, in inline functions of a
+    // header -- outside the reach of a pragma here, so without the Makefile's -ffp-contract=off they fuse.  The operators under the
+    // pragma do not: built with no contraction flag at all (hipcc's default honours pragmas) this function has no fma where
+    // k_view_transforms has four.  (An explicit -ffp-contract=fast overrides pragmas by definition.)
+#pragma clang fp contract(off)
+    const float fa = __uint_as_float(a), fb = __uint_as_float(b);
+    const float d = fb - fa;
+    const float p = t * d;
+    return __float_as_uint(fa + p);
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_path_blend(PathBlendArgs g) {
+    const uint32_t *__restrict__ const a = g.mode == PATH_BLEND_COPY_B ? g.b : g.a;  // (the ONE stream of a copy mode)
+    const uint32_t *__restrict__ const b = g.b;
+    uint32_t *__restrict__ const out = g.out;
+    const bool mix = g.mode == PATH_BLEND_MIX;
+    const uint32_t first = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
+    if (VEC) {
+        const uint32_t n4 = g.n >> 2;
+        const uint4 *a4 = reinterpret_cast<const uint4 *>(a), *b4 = reinterpret_cast<const uint4 *>(b);
+        uint4 *o4 = reinterpret_cast<uint4 *>(out);
+        for (uint32_t i = first; i < n4; i += stride) {
+            uint4 v = a4[i];
+            if (mix) {
+                const uint4 w = b4[i];
+                v = make_uint4(path_blend_word(v.x, w.x, g.t), path_blend_word(v.y, w.y, g.t), path_blend_word(v.z, w.z, g.t),
+                               path_blend_word(v.w, w.w, g.t));
+            }
+            o4[i] = v;
+        }
+        const uint32_t i = (n4 << 2) + first;  // the words behind the last whole quad
+        if (first < 3u && i < g.n) out[i] = mix ? path_blend_word(a[i], b[i], g.t) : a[i];
+    } else {
+        for (uint32_t i = first; i < g.n; i += stride) out[i] = mix ? path_blend_word(a[i], b[i], g.t) : a[i];
+    }
+}
+
+void launch_path_blend(const Frame &f, hipStream_t s) {
+    PathBlendArgs g{};
+    g.a = f.pd_a;
+    g.b = f.pd_b;
+    g.out = const_cast<uint32_t *>(f.scene) + f.pd_base;
+    g.n = f.cfg.layout.draw_tag_base - f.cfg.layout.path_data_base;
+    g.mode = f.pd_mode;
+    g.t = f.pd_t;
+    if (g.n == 0u) return;  // (a scene without path data)
+    // the scalar / vector split, decided here: the addresses of the streams the mode reads and of the copy
+    uintptr_t bits = reinterpret_cast<uintptr_t>(g.out);
+    if (g.mode != PATH_BLEND_COPY_B) bits |= reinterpret_cast<uintptr_t>(g.a);
+    if (g.mode != PATH_BLEND_COPY_A) bits |= reinterpret_cast<uintptr_t>(g.b);
+    const bool vec = (bits & 15u) == 0u;
+    const uint32_t per_wg = vec ? PATH_BLEND_VEC_WORDS : 256u;
+    uint32_t wgs = (uint32_t)(((uint64_t)g.n + per_wg - 1u) / per_wg);
+    if (wgs > PATH_BLEND_MAX_WGS) wgs = PATH_BLEND_MAX_WGS;
+    if (vec) hipLaunchKernelGGL(k_path_blend<true>, dim3(wgs), dim3(256), 0, s, g);
+    else hipLaunchKernelGGL(k_path_blend<false>, dim3(wgs), dim3(256), 0, s, g);
 }
 
 // k_compose_scene: a frame's packed scene written from instances of the library's fragments (vello_hip_render_instances; the contract is

@@ -71,6 +71,8 @@ int size_slot(vello_hip_ctx *c, SceneSlot &sc, const vello_hip_layout &L, size_t
     sc.dd_at = sc.view_at + xf_tail_words;
     sc.dd_sets = dd_sets;
     sc.dd_set_words = dd_words;
+    sc.pd_sets = 0u;  // (room for morphed frames' path data is made when the scene is first morphed: ensure_morph_room)
+    sc.i16_segments = false;
     sc.layout = L;
     sc.scene_len = scene_len;
     uint32_t n_path_tags = (L.path_data_base - L.path_tag_base) * 4u;
@@ -373,6 +375,23 @@ int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *sc
             return VELLO_HIP_E_INVALID;
         }
     }
+    if (&sc == &c->shared) {
+        // a segment tag whose points are pairs of i16 (path_tag.rs: PATH_TAG_F32 clear): such a scene's path-data words cannot be
+        // blended as floats (vello_hip_render_resident_morphed, rule 4).  Only the shared slot's frames can be morphed, so only its
+        // uploads look.  Four tags a word, no branch and no early exit -- an OR over the stream that the compiler vectorises: bit 0 of
+        // every byte of `seg` is "a segment" (either bit of the type field), of `f32` PATH_TAG_F32.
+        static_assert(PATH_TAG_SEG_TYPE == 3u && PATH_TAG_F32 == 8u, "the bit tricks below");
+        const uint8_t *tags = scene + (size_t)L.path_tag_base * 4u;
+        const size_t n_words = (size_t)L.path_data_base - L.path_tag_base;
+        uint32_t any = 0u;
+        for (size_t i = 0; i < n_words; i++) {
+            uint32_t w;
+            std::memcpy(&w, tags + i * 4u, 4);
+            const uint32_t seg = (w | (w >> 1)) & 0x01010101u, f32 = (w >> 3) & 0x01010101u;
+            any |= seg & ~f32;
+        }
+        sc.i16_segments = any != 0u;
+    }
     if (scene_len) HIP_TRY(c, hipMemcpyAsync(sc.scene.ptr, scene, scene_len, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync((char *)sc.scene.ptr + scene_len, 0, 64, st));
     sc.n_ramps = 0;
@@ -386,9 +405,90 @@ int load_slot(vello_hip_ctx *c, SceneSlot &sc, hipStream_t st, const uint8_t *sc
     return VELLO_HIP_OK;
 }
 
+// Room for the per-lane copies of the shared scene's path-data stream (SceneSlot::pd_at), made at most once per resident scene: by
+// vello_hip_upload_path_keyframes or by the first morphed frame.  The copies go behind the transform copies in the tail of the
+// scene's allocation; where the tail is too short the scene moves into a larger allocation -- bytes, slack and transform copies as
+// they are -- which waits for the frames in flight and counts as a scene allocation.  A buffer that has held a morphed scene of
+// this size keeps its tail (ensure_scene never shrinks it): the next such scene allocates nothing.  VELLO_HIP_E_INVALID, nothing
+// changed, for a scene whose copies would lie beyond a u32 word offset from its start.
+int ensure_morph_room(vello_hip_ctx *c) {
+    SceneSlot &sc = c->shared;
+    if (sc.pd_sets != 0u) return 0;
+    const uint32_t n = sc.layout.draw_tag_base - sc.layout.path_data_base;
+    const uint64_t set_words = ((uint64_t)n + PD_SLACK_WORDS + 3u) & ~(uint64_t)3u;
+    const uint64_t pd_at = ((uint64_t)sc.view_at + (uint64_t)sc.view_set_words * sc.view_sets + 3u) & ~(uint64_t)3u;
+    if (pd_at + set_words * MAX_LANES > 0xffffffffull) {
+        c->last_error = "the scene is too large for per-frame path data (its bytes and copies together must lie within 2^32 words)";
+        return VELLO_HIP_E_INVALID;
+    }
+    const size_t tail = (size_t)(pd_at - sc.view_at + set_words * MAX_LANES) * 4u;
+    int r;
+    if ((r = sync_all(c))) return r;
+    if (sc.view_cap_bytes < tail) {
+        const size_t at = sc.view_at * 4u;
+        void *grown = nullptr;
+        HIP_TRY(c, hipMalloc(&grown, at + tail + 256));
+        const hipError_t e = hipMemcpy(grown, sc.scene.ptr, at + sc.view_cap_bytes, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(grown);
+            c->last_error = std::string("path-data copies: ") + hipGetErrorString(e);
+            return VELLO_HIP_E_HIP;
+        }
+        HIP_TRY(c, hipFree(sc.scene.ptr));
+        sc.scene.ptr = grown;
+        sc.view_cap_bytes = tail;
+        c->scene_allocations++;
+    }
+    // every copy's slack: the words that follow the stream in the scene (the scene's own slack makes them PD_SLACK_WORDS)
+    uint32_t *words = (uint32_t *)sc.scene.ptr;
+    for (uint32_t k = 0; k < MAX_LANES; k++)
+        HIP_TRY(c, hipMemcpy(words + pd_at + k * set_words + n, words + sc.layout.draw_tag_base, PD_SLACK_WORDS * 4u, hipMemcpyDeviceToDevice));
+    sc.pd_at = (size_t)pd_at;
+    sc.pd_set_words = (uint32_t)set_words;
+    sc.pd_sets = MAX_LANES;
+    return 0;
+}
+
 }  // namespace vk
 
 extern "C" {
+
+uint32_t vello_hip_path_data_words(vello_hip_ctx *c) {
+    return c && c->shared.resident ? c->shared.layout.draw_tag_base - c->shared.layout.path_data_base : 0u;
+}
+
+// Keyframes for vello_hip_render_resident_morphed: copied once into a buffer of the context's; the frames that may still read the
+// set this one replaces are waited for, as an upload waits.  Everything that can refuse the call is asked before anything changes.
+int vello_hip_upload_path_keyframes(vello_hip_ctx *c, const uint32_t *words, uint32_t n_keys, uint32_t n_words) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    auto refuse = [&](const char *why) {
+        c->last_error = std::string("upload_path_keyframes: ") + why;
+        return VELLO_HIP_E_INVALID;
+    };
+    if (!c->shared.resident) return refuse("no scene uploaded");
+    if (n_words != vello_hip_path_data_words(c)) return refuse("n_words is not vello_hip_path_data_words of the resident scene");
+    if (n_keys > 0u && !words) return refuse("words is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int r;
+    if ((r = sync_all(c))) return r;
+    if (n_keys == 0u) {
+        c->n_keys = 0u;
+        return VELLO_HIP_OK;
+    }
+    if ((r = ensure_morph_room(c))) return r;
+    // on the device a keyframe begins on a 16-byte boundary whatever its length, so that k_path_blend reads every one of them with
+    // 16-byte accesses: rows of key_stride words
+    const uint32_t stride = (uint32_t)(((uint64_t)n_words + 3u) & ~(uint64_t)3u);
+    const size_t bytes = (size_t)n_keys * stride * 4u;
+    // from here on a failure leaves no keyframes
+    c->n_keys = 0u;
+    if ((r = ensure(c, c->keyframes, bytes ? bytes : 16u))) return r;
+    if (n_words)
+        HIP_TRY(c, hipMemcpy2D(c->keyframes.ptr, (size_t)stride * 4u, words, (size_t)n_words * 4u, (size_t)n_words * 4u, n_keys, hipMemcpyHostToDevice));
+    c->key_stride = stride;
+    c->n_keys = n_keys;
+    return VELLO_HIP_OK;
+}
 
 int vello_hip_upload_scene(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                            const uint32_t *ramps, uint32_t n_ramps) {
@@ -398,6 +498,7 @@ int vello_hip_upload_scene(vello_hip_ctx *c, const uint8_t *scene, size_t scene_
     // frames still in flight read the old scene
     if ((r = sync_all(c))) return r;
     c->have_fragments = false;  // (vello_hip_upload_fragments sets its table once the scene is resident)
+    c->n_keys = 0u;             // (path keyframes speak for the scene they were uploaded for)
     c->have_masks = false;
     c->frag_masks_host.clear();
     c->fragments.clear();
@@ -425,6 +526,7 @@ int vello_hip_upload_fragments(vello_hip_ctx *c, const uint8_t *scene, size_t sc
     // whatever goes wrong from here on, nothing stays resident (frames in flight keep what they were enqueued with)
     c->shared.resident = false;
     c->have_fragments = false;
+    c->n_keys = 0u;
     c->have_masks = false;
     c->frag_masks_host.clear();
     c->fragments.clear();

@@ -169,6 +169,7 @@ uint32_t vello_hip_stage_constant(int which) {
     case VELLO_HIP_SHAPE_FINE_BUCKET_WORDS: return FINE_BUCKET_WORDS;
     case VELLO_HIP_SHAPE_FINE_BUCKETS: return FINE_WORK_BUCKETS;
     case VELLO_HIP_SHAPE_PTCL_INITIAL_ALLOC: return PTCL_INITIAL_ALLOC;
+    case VELLO_HIP_SHAPE_PATH_BLEND_VEC_WORDS: return PATH_BLEND_VEC_WORDS;
     default: return 0u;
     }
 }

@@ -31,6 +31,7 @@ E_CAPACITY = -4
 PICK_NONE = 0xFFFFFFFF  # VELLO_HIP_PICK_NONE: no draw object under the point / the frame was not composed from instances
 PICK_MAX_POINTS = 4096  # VELLO_HIP_PICK_MAX_POINTS
 REGION_TOUCHED, REGION_ENCLOSED = 1, 2  # VELLO_HIP_REGION_*: the two bits of a word of Engine.pick_rect
+PATH_DATA_SCENE, PATH_DATA_DEVICE = 0xFFFFFFFF, 0xFFFFFFFE  # VELLO_HIP_PATH_DATA_*: the sources of a morphed frame that are not keyframes
 
 
 class RenderParams:
@@ -50,6 +51,15 @@ def _view_floats(view):
     if len(coeffs) != 6:
         raise ValueError("a view transform has six coefficients [m0 m1 m2 m3 t0 t1]")
     return (ctypes.c_float * 6)(*[float(v) for v in coeffs])
+
+
+def path_data_view(packed, layout):
+    """The path-data words of a packed scene -- [path_data_base, draw_tag_base) of `layout` -- as a float32 view of `packed` (a
+    C-contiguous uint8 array: writing through the view edits the scene).  (x, y) pairs in a scene whose segment tags are all f32;
+    what Engine.upload_path_keyframes and Engine.render_resident(points=...) take has this length and this meaning."""
+    if not isinstance(packed, np.ndarray) or packed.dtype != np.uint8 or not packed.flags["C_CONTIGUOUS"]:
+        raise ValueError("packed is a C-contiguous uint8 array")
+    return packed.reshape(-1).view(np.float32)[layout.path_data_base: layout.draw_tag_base]
 
 
 INSTANCE_DTYPE = np.dtype([("fragment", "<u4"), ("transform", "<f4", (6,))])  # vello_hip_instance, 28 bytes
@@ -689,21 +699,90 @@ class Engine:
                        "front_max_tags", "front_max_draw_objects", "front_tiny_segments",
                        "fine_window_words", "fine_batch_fills", "fine_batch_segments", "fine_item_cap", "fine_simple_records", "fine_prefetch_reach",
                        "fine_slice_fills", "fine_slice_min_fills", "fine_slice_min_fills_in_flight", "fine_slice_fills_forced",
-                       "fine_slice_min_fills_forced", "fine_heavy_words", "fine_bucket_words", "fine_buckets", "ptcl_initial_alloc")
+                       "fine_slice_min_fills_forced", "fine_heavy_words", "fine_bucket_words", "fine_buckets", "ptcl_initial_alloc",
+                       "path_blend_vec_words")
 
     def stage_constants(self):
         """vello_hip_stage_constant: the sizes at which the pipeline's kernels and the host's launch switches cut their work (a test
         seam; include/vello_hip.h lists them), by name."""
         return {k: int(self._lib.vello_hip_stage_constant(i)) for i, k in enumerate(self.STAGE_CONSTANTS)}
 
-    def render_resident(self, width, height, base_color, aa, out=None, out_stride=None):
+    def path_data_words(self):
+        """vello_hip_path_data_words: words of the resident scene's path-data stream (0 when no scene is resident)."""
+        return int(self._lib.vello_hip_path_data_words(self._h))
+
+    def upload_path_keyframes(self, keyframes):
+        """vello_hip_upload_path_keyframes: K alternative path-data streams of the resident scene -- a [K, N] float32 or uint32 array
+        (N = path_data_words(); the words go in bit for bit), or None / an empty list to drop the set.  Waits for the frames in
+        flight; a second call replaces the set, an upload of a scene drops it."""
+        if keyframes is None or len(keyframes) == 0:
+            self._check(self._lib.vello_hip_upload_path_keyframes(self._h, None, 0, self.path_data_words()), "upload_path_keyframes")
+            return
+        k = np.asarray(keyframes)
+        if k.dtype not in (np.dtype(np.float32), np.dtype(np.uint32)):
+            raise ValueError("keyframes are float32 or uint32 words")
+        if k.ndim == 1:
+            k = k.reshape(1, -1)
+        if k.ndim != 2:
+            raise ValueError("keyframes are a [K, N] array")
+        k = np.ascontiguousarray(k)
+        self._check(self._lib.vello_hip_upload_path_keyframes(self._h, k.ctypes.data, k.shape[0], k.shape[1]), "upload_path_keyframes")
+
+    def render_resident(self, width, height, base_color, aa, out=None, out_stride=None, morph=None, points=None, src_stream=None,
+                        points_is_device=False):
         """vello_hip_render_resident.  `out`: a dense uint8 target of height * width * 4 bytes, or an [H, W, 4] view whose rows lie
-        stride(0) bytes apart (_target); `out_stride` (bytes) overrides the stride taken from it."""
+        stride(0) bytes apart (_target); `out_stride` (bytes) overrides the stride taken from it.
+        `morph` = (src_a, src_b, t) makes it vello_hip_render_resident_morphed: this frame's path-data words are
+        A + t * (B - A) in f32 (A verbatim at t == 0 or src_a == src_b, B verbatim at t == 1).  A source is a keyframe index of
+        upload_path_keyframes, PATH_DATA_SCENE (the resident scene's own points) or PATH_DATA_DEVICE, which names `points`: a
+        float32 tensor of path_data_words() elements on the engine's GPU, or its address as an int -- the host never reads it.
+        `points` alone is morph=(PATH_DATA_DEVICE, PATH_DATA_DEVICE, 0).  `points_is_device` says that a numpy array stands for
+        device memory (the emulated build only).  `src_stream` (a hipStream_t as an int, or a torch stream) is the stream that
+        writes `points`: the frame runs behind it, and it waits for the kernel that reads them."""
         p = self._params(width, height, base_color, aa)
         ptr, stride = None, 0
         if out is not None:
             ptr, stride, _ = _target(self._lib, out, width, height, device_only=True, stride=out_stride)
-        self._check(self._lib.vello_hip_render_resident(self._h, ctypes.byref(p), ptr, stride), "render_resident")
+        if morph is None and points is None and src_stream is None:
+            self._check(self._lib.vello_hip_render_resident(self._h, ctypes.byref(p), ptr, stride), "render_resident")
+            return
+        if morph is None:
+            morph = (PATH_DATA_DEVICE, PATH_DATA_DEVICE, 0.0)
+        src_a, src_b, t = morph
+        keep, pp = None, None
+        if points is None:
+            pass
+        elif isinstance(points, np.ndarray):
+            if not (points_is_device and is_emulated(self._lib)):
+                raise ValueError("a numpy array is host memory: per-frame points are a tensor on the GPU (a host uploads keyframes)")
+            if points.dtype not in (np.dtype(np.float32), np.dtype(np.uint32)):
+                raise ValueError("points are float32 words")
+            if not points.flags["C_CONTIGUOUS"]:
+                raise ValueError("points are contiguous")
+            if points.size != self.path_data_words():
+                raise ValueError(f"{points.size} floats for a scene of {self.path_data_words()} path-data words")
+            keep = points  # (its own address: a slice that starts one float in stays one)
+            pp = keep.ctypes.data
+        elif hasattr(points, "data_ptr"):
+            import torch
+
+            if points.dtype != torch.float32 or not points.is_contiguous() or not points.is_cuda:
+                raise ValueError("points are a contiguous float32 tensor on the GPU")
+            if points.numel() != self.path_data_words():
+                raise ValueError(f"{points.numel()} floats for a scene of {self.path_data_words()} path-data words")
+            pp = points.data_ptr()
+        else:
+            pp = int(points)
+        relay = None
+        if hasattr(src_stream, "cuda_stream"):
+            s, relay = _source_stream(src_stream)
+        else:
+            s = src_stream
+        r = self._lib.vello_hip_render_resident_morphed(self._h, int(src_a) & 0xFFFFFFFF, int(src_b) & 0xFFFFFFFF, ctypes.c_float(float(t)), pp,
+                                                        ctypes.c_void_p(int(s)) if s else None, ctypes.byref(p), ptr, stride)
+        if relay is not None:
+            relay[0].wait_stream(relay[1])
+        self._check(r, "render_resident_morphed")
 
     def render(self, packed, layout, width, height, base_color, aa, ramps=None, out=None, out_stride=None, out_is_device=None):
         """One blocking frame; returns (HxWx4 uint8 image, bump dict).  With `out` (a target as render_resident takes it; a host
