@@ -150,7 +150,7 @@ enum {
     VELLO_HIP_BUF_TILES,         /* Tile[], 8 B */
     VELLO_HIP_BUF_SEG_COUNTS,    /* SegmentCount[], 8 B */
     VELLO_HIP_BUF_SEGMENTS,      /* PathSegment[], 24 B */
-    VELLO_HIP_BUF_PTCL,          /* u32[] */
+    VELLO_HIP_BUF_PTCL,          /* u32[] (after a frame with a damage rectangle: stale words in the blocks of tiles outside its window) */
     VELLO_HIP_BUF_BLEND_SPILL,   /* u32[] */
     VELLO_HIP_BUF_OUTPUT,        /* internal RGBA8 target, width*height*4 */
     VELLO_HIP_BUF_COUNT
@@ -321,6 +321,40 @@ int vello_hip_set_viewport_cull(vello_hip_ctx *ctx, int enabled);
  * view, into a per-frame copy behind the scene's bytes; nothing crosses PCIe.  Scenes whose packed bytes and copies together
  * exceed 2^32 words are refused with VELLO_HIP_E_INVALID when a frame with a view is enqueued. */
 int vello_hip_set_view_transform(vello_hip_ctx *ctx, const float view[6] /* nullable: off (default) */);
+/* Damage rectangle for the frames that follow (default: none -- every frame draws its whole target).  `rect` is x0 y0 x1 y1 in
+ * pixels, half open: a frame enqueued while one is set renders only the tiles the rectangle touches and writes only its pixels --
+ * partial redraw for a caller that knows what changed (a highlight, a moved handle, a caret).  The engine does not compute damage.
+ *   1. THE RECTANGLE.  R = rect cut to [0, width) x [0, height), computed per frame against that frame's target size.  x0 > x1 or
+ *      y0 > y1 is VELLO_HIP_E_INVALID (vello_hip_last_error names the rule) and nothing changes: the setting, the rotation, every
+ *      frame in flight.  An EMPTY R is legal (zero area, or wholly off the target): such a frame writes no byte of the target
+ *      and launches neither k_coarse, k_path_tiling nor k_fine.  NULL restores whole frames bit for bit, in every buffer and
+ *      counter; a rectangle that covers the whole target gives the off state's image, buffers and counters.
+ *   2. THE TARGET.  The engine writes exactly the bytes [y * out_stride + x0 * 4, y * out_stride + x1 * 4) of the rows
+ *      y0 <= y < y1 of R, and no other byte (this extends THE TARGET at vello_hip_render_resident: everything beside R keeps its
+ *      contents like row padding does).  Every pixel of R holds the value the whole frame would have written there -- MSAA8 /
+ *      MSAA16 bit for bit, area AA within the order of a tile's segment atomics, as for any two whole frames.  The blocking
+ *      vello_hip_render with a host target copies R's rows and columns only.  With out_device == NULL the frame writes R into its
+ *      lane's internal target; the internal targets of different lanes (vello_hip_set_frames_in_flight) are DIFFERENT surfaces,
+ *      so partial frames want a caller's target or one frame in flight.
+ *   3. EVERYTHING AHEAD OF COARSE IS THE WHOLE FRAME'S: tag monoids, path boxes, the line soup, draw monoids, info, clip boxes,
+ *      bin lists, Path records, tile backdrops, SegmentCount records, and bump.lines / binning / tile / seg_counts.  (The soup
+ *      and the backdrops of tiles left of R feed R's backdrops.)  vello_hip_pick and vello_hip_pick_rect after a damaged frame
+ *      therefore answer as after the whole frame.  k_coarse_prep runs whole.
+ *   4. BEHIND IT, with W = the tiles that intersect R: a tile outside W gets nothing -- no PTCL word, no segment slice, no
+ *      blend-spill allocation, no bucket entry, no slice item; a tile inside W gets the command list, the segments and the blend
+ *      offset the whole frame gives it.  bump.segments, bump.ptcl and bump.blend count W's tiles only, so the segment, PTCL and
+ *      blend pools overflow (VELLO_HIP_E_CAPACITY, auto-grow's demand) on the smaller counts: a window of a frame fits pools the
+ *      whole frame overflows.  vello_hip_estimate_capacities is unchanged (still an upper bound).  VELLO_HIP_BUF_PTCL: the blocks
+ *      of tiles outside W hold stale words of earlier frames (word 0 of the buffer: tile 0's blend offset, or 0 when tile 0 is
+ *      outside W).
+ *   5. Composes with viewport culling, a view, instances, retained poses and paints, a morph, VELLO_HIP_DEBUG_NO_CULL, forced
+ *      slices and frames in flight; none of them learns about it.
+ *   6. Applies to frames enqueued after the call on every entry point that renders (render, render_frame, render_resident,
+ *      render_resident_morphed, render_instances[_painted], render_retained[_painted], and run_stages when the range holds COARSE,
+ *      PATH_TILING or FINE) and on all in-flight buffer sets; frames already enqueued keep the rectangle they were enqueued with:
+ *      four frames in flight may carry four rectangles.
+ * VELLO_HIP_E_INVALID for a null context. */
+int vello_hip_set_damage_rect(vello_hip_ctx *ctx, const uint32_t rect[4] /* x0 y0 x1 y1, pixels, half-open; nullable: off (default) */);
 /* vello_hip_estimate_capacities with V composed, by the same formula, into every transform the estimator reads; equal to it for
  * view == NULL.  VELLO_HIP_E_INVALID for a view with a NaN or infinite entry. */
 int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,

@@ -196,6 +196,7 @@ unsafe extern "C" {
     pub fn vello_hip_scene_allocations(ctx: *mut vello_hip_ctx) -> u64;
     pub fn vello_hip_scene_index_builds(ctx: *mut vello_hip_ctx) -> u64;
     pub fn vello_hip_set_view_transform(ctx: *mut vello_hip_ctx, view: *const f32) -> c_int;
+    pub fn vello_hip_set_damage_rect(ctx: *mut vello_hip_ctx, rect: *const u32) -> c_int;
     pub fn vello_hip_estimate_capacities_view(scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, params: *const vello_hip_render_params, view: *const f32, out: *mut vello_hip_capacities) -> c_int;
     pub fn vello_hip_set_debug_flags(ctx: *mut vello_hip_ctx, flags: u32) -> c_int;
     pub fn vello_hip_set_frames_in_flight(ctx: *mut vello_hip_ctx, n: u32) -> c_int;

@@ -138,6 +138,7 @@ def load_library():
     sig("vello_hip_set_auto_grow", i32, [vp, i32])
     sig("vello_hip_set_viewport_cull", i32, [vp, i32])
     sig("vello_hip_set_view_transform", i32, [vp, c.POINTER(c.c_float)])
+    sig("vello_hip_set_damage_rect", i32, [vp, c.POINTER(u32)])
     sig("vello_hip_set_debug_flags", i32, [vp, u32])
     sig("vello_hip_last_render_attempts", u32, [vp])
     sig("vello_hip_fused_launches", ctypes.c_uint64, [vp])

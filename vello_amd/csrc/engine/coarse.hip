@@ -38,9 +38,23 @@
 //    same batch can be seen in time: the list is restarted at that draw and the covered draws of the batch are dropped.
 #include "engine.h"
 
+// VK_COARSE_DAMAGE (coarse_damage.hip compiles this file once more with it): k_coarse for frames whose damage rectangle is smaller
+// than their target (vello_hip_set_damage_rect), named k_coarse_damage -- one more argument, the tile window, and WIN = true in
+// coarse_workgroup.  A translation unit of its own, as fine's (fine.hip, VK_FINE_DAMAGE): the kernel of whole frames has no such
+// argument and is compiled as it was before there were windows.
+#ifdef VK_COARSE_DAMAGE
+#define k_coarse k_coarse_damage
+#endif
+
 namespace vk {
 
 namespace {
+
+#ifdef VK_COARSE_DAMAGE
+constexpr bool WIN = true;
+#else
+constexpr bool WIN = false;
+#endif
 
 constexpr uint32_t SUB_W = 8;         // a workgroup owns an 8x8-tile quadrant of a bin
 #ifndef VK_COARSE_NW
@@ -158,6 +172,7 @@ __device__ __forceinline__ bool coarse_back_to_front(bool allow_cull, uint32_t n
 
 }  // namespace
 
+#ifndef VK_COARSE_DAMAGE
 // Job (a), blocks [0, n_el_blocks): the per-draw-object record.  Job (b), the remaining blocks: the tile bit planes.
 __global__ void __launch_bounds__(256) k_coarse_prep(Config cfg, uint32_t n_el_blocks, const uint32_t *__restrict__ scene,
                                                      const DrawMonoid *__restrict__ draw_monoids, const uint32_t *__restrict__ info_bin_data,
@@ -214,6 +229,7 @@ __global__ void __launch_bounds__(256) k_coarse_prep(Config cfg, uint32_t n_el_b
         }
     }
 }
+#endif  // VK_COARSE_DAMAGE
 
 
 // coarse.wgsl:156-471.  512 threads: as draw objects while the bin's list is filtered, as 8 x 64 (tile, object) pairs
@@ -229,8 +245,15 @@ __global__ void __launch_bounds__(256) k_coarse_prep(Config cfg, uint32_t n_el_b
 // the current region's commands, or into a new region [slack | words | CMD_JUMP head].  The batch in which a tile is
 // covered, or the last batch of the stream, completes the tile's list: its words go into the tile's fixed block when they
 // fit, followed by the jump to the head (CMD_END when there is none).
+// win: the tiles the frame draws (Frame::damage's window W, cut to the target; the whole target without a damage rectangle).  The
+// grid holds the bins that meet W only; a quadrant that does not meet it leaves at once; in one that does, a tile outside W is
+// what a tile outside the target is: no object's rectangle reaches it, back to front it is covered from the start, and it gets no
+// list end, blend offset, bucket entry or slice item.
+// WIN = false (this file compiled on its own) is the form of frames that draw their whole target -- every frame without a damage
+// rectangle: `win` is not read and the code is what it was before there were windows (profiles/damage_rect.txt says why it is
+// not a run-time window that happens to be the target).
 template <bool B2F>
-__device__ __forceinline__ void coarse_workgroup(CoarseLds &sh, const Config &cfg, const uint32_t *__restrict__ scene, const BinHeader *__restrict__ bin_headers,
+__device__ __forceinline__ void coarse_workgroup(CoarseLds &sh, const Config &cfg, const TileRect win, const uint32_t *__restrict__ scene, const BinHeader *__restrict__ bin_headers,
                                                 const uint32_t *__restrict__ info_bin_data, const CoarseEl *__restrict__ coarse_el,
                                                 const uint32_t *__restrict__ tile_bits, Tile *tiles, Bump *bump,
                                                 uint32_t *ptcl, bool allow_cull, uint32_t *work_count, uint32_t *tile_order,
@@ -246,18 +269,35 @@ __device__ __forceinline__ void coarse_workgroup(CoarseLds &sh, const Config &cf
             return;
         }
     }
+    // ptcl[0] is tile 0's blend offset and k_path_tiling's "the frame failed" mark (~0: k_fine leaves).  A window without tile 0
+    // writes no word of that tile, so an earlier frame's mark would still stand there: cleared by one plain store.
+    if (WIN && blockIdx.x == 0 && tid == 0 && (win.x0 | win.y0) != 0u) ptcl[0] = 0u;
     const uint32_t width_in_bins = (cfg.width_in_tiles + N_TILE_X - 1u) / N_TILE_X;
     const uint32_t height_in_bins = (cfg.height_in_tiles + N_TILE_Y - 1u) / N_TILE_Y;
     const uint32_t n_bins = width_in_bins * height_in_bins;
     // workgroup -> (bin, quadrant): consecutive workgroup ids go to different XCDs (id mod 8), so the four quadrants
-    // of a bin, which read the same bin lists and records, get ids that are equal mod 8 and share one L2
-    const uint32_t bin_ix = ((blockIdx.x >> 3) >> 2) * 8u + (blockIdx.x & 7u);
+    // of a bin, which read the same bin lists and records, get ids that are equal mod 8 and share one L2.  The grid counts the
+    // bins of the window's bin rectangle, row by row (all bins when the window is the target).
+    const uint32_t win_bx0 = WIN ? win.x0 / N_TILE_X : 0u, win_by0 = WIN ? win.y0 / N_TILE_Y : 0u;
+    const uint32_t win_bw = WIN ? (win.x1 + N_TILE_X - 1u) / N_TILE_X - win_bx0 : width_in_bins;
+    const uint32_t win_bh = WIN ? (win.y1 + N_TILE_Y - 1u) / N_TILE_Y - win_by0 : height_in_bins;
+    const uint32_t win_bin = ((blockIdx.x >> 3) >> 2) * 8u + (blockIdx.x & 7u);
     const uint32_t quad = (blockIdx.x >> 3) & 3u;
-    if (bin_ix >= n_bins) return;
+    if (win_bin >= win_bw * win_bh) return;
+    const uint32_t bin_x = win_bx0 + win_bin % win_bw, bin_y = win_by0 + win_bin / win_bw;
+    const uint32_t bin_ix = WIN ? bin_y * width_in_bins + bin_x : win_bin;
     const uint32_t aligned_n_bins = (n_bins + N_TILE - 1u) & ~(N_TILE - 1u);
     const uint32_t n_partitions = (cfg.layout.n_draw_objects + N_TILE - 1u) / N_TILE;
-    const uint32_t sub_x0 = N_TILE_X * (bin_ix % width_in_bins) + SUB_W * (quad & 1u);
-    const uint32_t sub_y0 = N_TILE_Y * (bin_ix / width_in_bins) + SUB_W * (quad >> 1);
+    const uint32_t sub_x0 = N_TILE_X * bin_x + SUB_W * (quad & 1u);
+    const uint32_t sub_y0 = N_TILE_Y * bin_y + SUB_W * (quad >> 1);
+    // the window inside the quadrant, in quadrant-local tiles; a quadrant it does not reach has nothing to do
+    // (whole frames: the quadrant, and a tile is in the window when it is in the target)
+    const int32_t wx0 = WIN ? clampi((int32_t)win.x0 - (int32_t)sub_x0, 0, (int32_t)SUB_W) : 0, wx1 = WIN ? clampi((int32_t)win.x1 - (int32_t)sub_x0, 0, (int32_t)SUB_W) : (int32_t)SUB_W;
+    const int32_t wy0 = WIN ? clampi((int32_t)win.y0 - (int32_t)sub_y0, 0, (int32_t)SUB_W) : 0, wy1 = WIN ? clampi((int32_t)win.y1 - (int32_t)sub_y0, 0, (int32_t)SUB_W) : (int32_t)SUB_W;
+    if (WIN && (wx0 >= wx1 || wy0 >= wy1)) return;
+    // (whole frames: whether the tile is in the target, worked out where it is asked as it always was -- in_window below)
+    const bool in_win = WIN && (int32_t)(lane % SUB_W) >= wx0 && (int32_t)(lane % SUB_W) < wx1 && (int32_t)(lane / SUB_W) >= wy0 && (int32_t)(lane / SUB_W) < wy1;
+    auto in_window = [&]() -> bool { return WIN ? in_win : sub_x0 + lane % SUB_W < cfg.width_in_tiles && sub_y0 + lane / SUB_W < cfg.height_in_tiles; };
     const bool has_clips = !B2F && cfg.layout.n_clips != 0u;
     const bool cull = B2F || (allow_cull && !has_clips);
     const uint32_t ptcl_dyn_start = cfg.width_in_tiles * cfg.height_in_tiles * PTCL_INITIAL_ALLOC;
@@ -286,8 +326,9 @@ __device__ __forceinline__ void coarse_workgroup(CoarseLds &sh, const Config &cf
     uint32_t fills_total = 0u;       // CMD_FILLs among them
     uint32_t clip_zero_depth = 0u, clip_depth = 0u, render_blend_depth = 0u, max_blend_depth = 0u;
     // back to front: the same in every wave (lane = tile) -- the tile's list is complete, nothing in front of it matters.
-    // Tiles outside the target count as covered from the start: nothing touches them, and they must not hold up the exit.
-    bool covered = B2F && !(sub_x0 + lane % SUB_W < cfg.width_in_tiles && sub_y0 + lane / SUB_W < cfg.height_in_tiles);
+    // Tiles outside the window (it lies inside the target; whole frames: outside the target) count as covered from the start: nothing touches them, and they must
+    // not hold up the exit.
+    bool covered = B2F && !in_window();
     u64 covered_mask = B2F ? __ballot(covered) : 0ull;  // ... as the object-side threads see it (bit = tile)
     // back to front, wave 0: the first command word of the list built so far (NONE: nothing yet), the free words in front of
     // it in its region, and whether the fixed block has been written
@@ -383,8 +424,9 @@ __device__ __forceinline__ void coarse_workgroup(CoarseLds &sh, const Config &cf
             const int32_t bx0 = (int32_t)(el.bbox_x & 0xffffu), bx1 = (int32_t)(el.bbox_x >> 16);
             const int32_t by0 = (int32_t)(el.bbox_y & 0xffffu), by1 = (int32_t)(el.bbox_y >> 16);
             const int32_t dx = bx0 - (int32_t)sub_x0, dy = by0 - (int32_t)sub_y0;
-            const int32_t x0 = clampi(dx, 0, (int32_t)SUB_W), y0 = clampi(dy, 0, (int32_t)SUB_W);
-            const int32_t x1 = clampi(bx1 - (int32_t)sub_x0, 0, (int32_t)SUB_W), y1 = clampi(by1 - (int32_t)sub_y0, 0, (int32_t)SUB_W);
+            // (cut to the window as to the quadrant: no command and no segment slice reaches a tile outside it)
+            const int32_t x0 = clampi(dx, wx0, wx1), y0 = clampi(dy, wy0, wy1);
+            const int32_t x1 = clampi(bx1 - (int32_t)sub_x0, wx0, wx1), y1 = clampi(by1 - (int32_t)sub_y0, wy0, wy1);
             const bool meets = el.tag != DRAWTAG_NOP && x1 > x0 && y1 > y0;
             const uint32_t stride = (uint32_t)(bx1 - bx0);
             const uint32_t base = el.tiles - (uint32_t)(dy * (int32_t)stride + dx);
@@ -803,7 +845,7 @@ __device__ __forceinline__ void coarse_workgroup(CoarseLds &sh, const Config &cf
         }
     }
     if (wave == 0u) {
-        const bool in_target = sub_x0 + lane % SUB_W < cfg.width_in_tiles && sub_y0 + lane / SUB_W < cfg.height_in_tiles;
+        const bool in_target = in_window();  // (the window lies inside the target; whole frames: in the target)
         if (in_target) {
             if (B2F) {  // no batch completed the list (an empty stream, or one that ended on a full batch)
                 if (!dead && !finished) *reinterpret_cast<PtclWords2 *>(ptcl + list_start) = head == NONE ? PtclWords2{CMD_END, 0u} : PtclWords2{CMD_JUMP, head};
@@ -872,8 +914,13 @@ __device__ __forceinline__ void coarse_workgroup(CoarseLds &sh, const Config &cf
 }
 
 // One launch, two forms: which one follows from the scene (k_coarse_prep's flag), not from anything the host knows when it
-// enqueues the frame.  The choice is uniform over the launch.
-__global__ void __launch_bounds__(WG) k_coarse(Config cfg, const uint32_t *__restrict__ scene, const BinHeader *__restrict__ bin_headers,
+// enqueues the frame.  The choice is uniform over the launch.  (k_coarse_damage: `win`, the frame's tile window.)
+#ifdef VK_COARSE_DAMAGE
+#define COARSE_WIN_PARAM TileRect win,
+#else
+#define COARSE_WIN_PARAM
+#endif
+__global__ void __launch_bounds__(WG) k_coarse(Config cfg, COARSE_WIN_PARAM const uint32_t *__restrict__ scene, const BinHeader *__restrict__ bin_headers,
                                                 const uint32_t *__restrict__ info_bin_data, const CoarseEl *__restrict__ coarse_el,
                                                 const uint32_t *__restrict__ tile_bits, Tile *tiles, Bump *bump,
                                                 uint32_t *ptcl, bool allow_cull, const uint32_t *__restrict__ opaque_fills, uint32_t *work_count,
@@ -886,18 +933,26 @@ __global__ void __launch_bounds__(WG) k_coarse(Config cfg, const uint32_t *__res
     extern __shared__ __attribute__((aligned(16))) unsigned char coarse_lds_raw[];
     CoarseLds &sh = *reinterpret_cast<CoarseLds *>(coarse_lds_raw);
 #endif
+#ifndef VK_COARSE_DAMAGE
+    const TileRect win{0u, 0u, 0u, 0u};  // (not read)
+#endif
     const uint32_t my_shard = (threadIdx.x & 63u) < COARSE_OPAQUE_SHARDS ? opaque_fills[threadIdx.x & 63u] : 0u;
     if (coarse_back_to_front(allow_cull, cfg.layout.n_clips, __ballot(my_shard != 0u) != 0ull))
-        coarse_workgroup<true>(sh, cfg, scene, bin_headers, info_bin_data, coarse_el, tile_bits, tiles, bump, ptcl, allow_cull, work_count, tile_order, slice_items,
+        coarse_workgroup<true>(sh, cfg, win, scene, bin_headers, info_bin_data, coarse_el, tile_bits, tiles, bump, ptcl, allow_cull, work_count, tile_order, slice_items,
                                slice_counters, slice_cap, cov_cap, slice_fills, slice_min_fills);
     else
-        coarse_workgroup<false>(sh, cfg, scene, bin_headers, info_bin_data, coarse_el, tile_bits, tiles, bump, ptcl, allow_cull, work_count, tile_order, slice_items,
+        coarse_workgroup<false>(sh, cfg, win, scene, bin_headers, info_bin_data, coarse_el, tile_bits, tiles, bump, ptcl, allow_cull, work_count, tile_order, slice_items,
                                 slice_counters, slice_cap, cov_cap, slice_fills, slice_min_fills);
 }
 
 // k_coarse's dynamic LDS is beyond the 64 KB a kernel gets without asking; function attributes are per device, so every
 // context asks once for its own (vello_hip_create, after hipSetDevice) and reports a refusal there.
+#ifdef VK_COARSE_DAMAGE
+int enable_coarse_damage_lds() {
+#else
 int enable_coarse_lds() {
+    if (int e = enable_coarse_damage_lds()) return e;
+#endif
 #ifndef VELLO_SIMT_EMU
     return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(k_coarse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(CoarseLds));
 #else
@@ -905,6 +960,14 @@ int enable_coarse_lds() {
 #endif
 }
 
+#ifdef VK_COARSE_DAMAGE
+// k_coarse_damage over n_wg workgroups: the bins that meet `win` (launch_coarse sizes the grid)
+void launch_coarse_damage(const Frame &f, hipStream_t s, uint32_t n_wg, TileRect win) {
+    hipLaunchKernelGGL(k_coarse, dim3(n_wg), dim3(WG), sizeof(CoarseLds), s, f.cfg, win, f.scene, f.bin_headers, f.info_bin_data, f.coarse_el, f.tile_bits,
+                       f.tiles, f.bump(), f.ptcl, !f.no_cull, f.control->opaque_fills, f.control->work_count, f.tile_order,
+                       f.slice_items, f.slice_counters, f.slice_cap, f.cov_cap, f.slice_fills, f.slice_min_fills);
+}
+#else
 constexpr uint32_t COARSE_GRID_BINS = 8u;  // k_coarse's grid is rounded up to this many bins (four workgroups each)
 uint32_t coarse_batch_draws() { return NB; }
 uint32_t coarse_grid_bins() { return COARSE_GRID_BINS; }
@@ -923,10 +986,21 @@ void launch_coarse(const Frame &f, hipStream_t s, hipEvent_t *mid) {
     hipLaunchKernelGGL(k_coarse_prep, dim3(n_el_blocks + n_bit_blocks), dim3(256), 0, s, dd_config(f), n_el_blocks, f.scene, f.draw_monoids,
                        f.info_bin_data, f.paths, f.tiles, f.bump(), f.coarse_el, f.tile_bits, f.control->opaque_fills);
     if (mid) (void)hipEventRecord(mid[0], s);
-    const uint32_t n_wg = ((wb * hb + COARSE_GRID_BINS - 1u) / COARSE_GRID_BINS) * COARSE_GRID_BINS * 4u;
+    // the bins that meet the frame's tile window (all of them without a damage rectangle); an empty window: no launch -- the
+    // control block's zeros are what fine and path_tiling then find (no bucket entry, no slice item, no segment slice)
+    const TileRect win = damage_window(f.damage);
+    const uint32_t win_bins = ((win.x1 + 15u) / 16u - win.x0 / 16u) * ((win.y1 + 15u) / 16u - win.y0 / 16u);
+    if (win_bins == 0u) return;
+    const uint32_t n_wg = ((win_bins + COARSE_GRID_BINS - 1u) / COARSE_GRID_BINS) * COARSE_GRID_BINS * 4u;
+    // (Frame::damaged picks the kernel: whole frames run the one that knows no window)
+    if (f.damaged) {
+        launch_coarse_damage(f, s, n_wg, win);
+        return;
+    }
     hipLaunchKernelGGL(k_coarse, dim3(n_wg), dim3(WG), sizeof(CoarseLds), s, f.cfg, f.scene, f.bin_headers, f.info_bin_data, f.coarse_el, f.tile_bits,
                        f.tiles, f.bump(), f.ptcl, !f.no_cull, f.control->opaque_fills, f.control->work_count, f.tile_order,
                        f.slice_items, f.slice_counters, f.slice_cap, f.cov_cap, f.slice_fills, f.slice_min_fills);
 }
+#endif
 
 }  // namespace vk

@@ -273,8 +273,10 @@ int vello_hip_create(int device, uint32_t aa_mask, const vello_hip_capacities *c
         if (caps->blend_spill) d.blend_spill = caps->blend_spill;
         if (caps->ptcl) d.ptcl = caps->ptcl;
     }
-    // path_tiling writes segments[] unguarded by a failure bit only when both pools match (coarse.wgsl:166)
-    if (d.segments < d.seg_counts) d.segments = d.seg_counts;
+    // A segment pool the caller did not size follows the seg_counts pool (a whole frame has a segment per SegmentCount record,
+    // coarse.wgsl:166).  One given explicitly is kept, smaller too: a frame with a damage rectangle needs the segments of its window
+    // only, and k_path_tiling fails a frame whose coarse handed out more than the pool holds.
+    if (d.segments < d.seg_counts && !(caps && caps->segments)) d.segments = d.seg_counts;
     c->caps = d;
     choose_lane_priority(c, lane_queues);
     auto fail = [&](const char *what) {

@@ -165,6 +165,7 @@ struct Lane {
     }
     bool used = false;
     bool slices_on = false;   // the lane's latest frame ran with fine's slices enabled (an MSAA frame)
+    bool frame_damaged = false;  // the lane's latest frame drew less than its target (Frame::damaged): its slice count is not the scene's
     uint32_t slice_cap_coarse = 0;  // slice blocks the lane's latest COARSE launch was told of (a later FINE must launch as many)
     uint32_t slice_fills_coarse = 0;  // ... and the slice size it cut with (0: no slices -- an area-AA frame)
     bool frame_indexed = false;  // the lane's latest frame read the shared slot's index (VELLO_HIP_BUF_TAG_MONOIDS shows its array)
@@ -240,6 +241,8 @@ struct vello_hip_ctx {
     bool viewport_cull = false;  // vello_hip_set_viewport_cull: copied into every Frame when it is prepared
     bool has_view = false;       // vello_hip_set_view_transform: likewise
     vk::Xform view{1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
+    bool has_damage = false;     // vello_hip_set_damage_rect: likewise; cut to the frame's target by prepare_frame (Frame::damage)
+    uint32_t damage[4] = {0u, 0u, 0u, 0u};  // x0 y0 x1 y1 as the caller gave them (x0 <= x1, y0 <= y1)
     hipStream_t copy_stream = nullptr;  // vello_hip_gather_frames: this context's peer copy
     hipEvent_t frame_done = nullptr;
     // vello_hip_write_image: atlas uploads are stream-ordered, not host-synchronous (wgpu's queue.write_texture is queued

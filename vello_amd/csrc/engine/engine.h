@@ -142,6 +142,17 @@ inline uint32_t flatten_arc_shard_cap(uint32_t n_seg_max, bool side_by_side) {
     return ((grid + FLATTEN_ARC_SHARDS - 1u) / FLATTEN_ARC_SHARDS) * (rounds < 1u ? 1u : rounds) * 256u;
 }
 
+// A damage rectangle (vello_hip_set_damage_rect) in pixels and the window of tiles that meet it, both half open.  Kernel arguments
+// of k_fine and k_coarse (wave-uniform); not part of Config, which is the reference's layout.
+struct PixelRect { uint32_t x0, y0, x1, y1; };
+struct TileRect { uint32_t x0, y0, x1, y1; };
+inline bool empty(const PixelRect &r) { return r.x0 >= r.x1 || r.y0 >= r.y1; }
+// W: the tiles that meet R (no tile for an empty R)
+inline TileRect damage_window(const PixelRect &r) {
+    if (empty(r)) return TileRect{0u, 0u, 0u, 0u};
+    return TileRect{r.x0 / TILE_WIDTH, r.y0 / TILE_HEIGHT, (r.x1 + TILE_WIDTH - 1u) / TILE_WIDTH, (r.y1 + TILE_HEIGHT - 1u) / TILE_HEIGHT};
+}
+
 struct Frame {
     Config cfg;  // host copy; kernels receive it by value
     uint32_t n_tag_words;
@@ -239,6 +250,11 @@ struct Frame {
     bool sequential_clip;  // VELLO_HIP_DEBUG_SEQ_CLIP: the one-wave stack machine whatever the clip count
     bool no_cull;  // VELLO_HIP_DEBUG_NO_CULL: coarse emits every draw, as the reference does (exact PTCL / segment diffs)
     bool viewport_cull;  // vello_hip_set_viewport_cull: flatten leaves lines off the target's top, bottom and right out of the soup (flatten.hip)
+    // vello_hip_set_damage_rect: R, the caller's rectangle cut to this frame's target (pixels, half open); the whole target when the
+    // option is off.  k_coarse builds lists for the tiles that meet R only (damage_window), k_fine stores R's pixels only; every
+    // stage ahead of coarse is the whole frame's.  damaged: R is smaller than the target.
+    PixelRect damage;
+    bool damaged;
     bool brushes;  // the scene has gradient / image / blurred-rect draw objects (selects fine's specialisation)
     const uint32_t *mask_lut8;
     const uint32_t *mask_lut16;
@@ -362,9 +378,15 @@ void launch_binning_tile_alloc(const Frame &f, hipStream_t s);
 void launch_path_count(const Frame &f, hipStream_t s);
 void launch_backdrop(const Frame &f, hipStream_t s);
 void launch_coarse(const Frame &f, hipStream_t s, hipEvent_t *mid = nullptr);
+// k_coarse_damage (coarse_damage.hip): k_coarse for a frame whose damage rectangle is smaller than its target, over the bins that meet
+// its tile window; launch_coarse hands such frames on.  enable_coarse_damage_lds: its share of enable_coarse_lds.
+void launch_coarse_damage(const Frame &f, hipStream_t s, uint32_t n_wg, TileRect win);
+int enable_coarse_damage_lds();
 int enable_coarse_lds();  // hipError_t of the per-device dynamic-LDS opt-in
 void launch_path_tiling(const Frame &f, hipStream_t s);
 void launch_fine(const Frame &f, hipStream_t s);
+// k_fine_damage (fine_damage.hip): fine for a frame whose damage rectangle is smaller than its target; launch_fine hands such frames on
+void launch_fine_damage(const Frame &f, hipStream_t s);
 // Test seam (vello_hip_stage_constant, seams.hip): the sizes that are named beside the kernels they belong to
 uint32_t coarse_batch_draws();          // coarse.hip NB: draw objects per batch of a bin's list
 uint32_t coarse_grid_bins();            // coarse.hip: k_coarse's grid holds a multiple of this many bins

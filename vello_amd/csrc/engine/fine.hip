@@ -15,6 +15,10 @@
 //  * each lane owns 4 horizontally adjacent pixels and stores them as one 16-byte write.
 #include "engine.h"
 
+#ifdef VK_FINE_DAMAGE
+#define k_fine k_fine_damage  // (this unit's kernels: see VK_FINE_DAMAGE at the kernel)
+#endif
+
 namespace vk {
 
 namespace {
@@ -1713,6 +1717,11 @@ __device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t
 #ifndef VK_FINE_WAVES_IN_FLIGHT
 #define VK_FINE_WAVES_IN_FLIGHT 5
 #endif
+// VK_FINE_DAMAGE (fine_damage.hip compiles this file once more with it): the kernels of frames whose damage rectangle is smaller
+// than their target (vello_hip_set_damage_rect), named k_fine_damage -- one more argument, `dmg`, and the final store held to it.
+// A translation unit of their own, with their own copies of the out-of-line functions: the kernels of whole frames are then the
+// code they were before there were rectangles.  (As a run-time rectangle that may be the target, and also as a template flag
+// beside them in one unit, they were not: the MSAA forms' spills moved -- profiles/damage_rect.txt.)
 template <int AA, bool BRUSHES, int WAVES = 4>
 __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, const Segment *__restrict__ segments, const uint32_t *__restrict__ ptcl,
                                              const uint32_t *__restrict__ info, uint32_t *blend_spill, uint8_t *__restrict__ output,
@@ -1720,7 +1729,11 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
                                              const uint32_t *__restrict__ mask_lut, const uint32_t *__restrict__ atlas_texels,
                                              uint32_t atlas_w, uint32_t atlas_h, const uint32_t *__restrict__ work_count,
                                              const uint32_t *__restrict__ tile_order, const SliceItem *__restrict__ slice_items,
-                                             uint32_t *slice_counters, uint32_t *cov, uint32_t slice_blocks, uint32_t slice_fills) {
+                                             uint32_t *slice_counters, uint32_t *cov, uint32_t slice_blocks, uint32_t slice_fills
+#ifdef VK_FINE_DAMAGE
+                                             , PixelRect dmg
+#endif
+                                             ) {
     __shared__ FineShared sh;
     __shared__ uint32_t sh_samples[AA == 2 ? 1024 : (AA == 1 ? 512 : 1)];
     __shared__ FineBatch bt;
@@ -2086,7 +2099,13 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
     // fine.wgsl:1386-1397: un-premultiplied RGBA8
     const uint32_t px0 = tile_x * TILE_WIDTH + lx * PIXELS_PER_THREAD;
     const uint32_t py = tile_y * TILE_HEIGHT + ly;
+#ifdef VK_FINE_DAMAGE
+    // dmg: the pixels the frame writes (Frame::damage: the damage rectangle cut to the target).  The tile is here because it meets
+    // the rectangle (coarse's window); the store is held to it: no byte outside [x0, x1) of the rows [y0, y1).
+    if (py >= dmg.y0 && py < dmg.y1 && px0 < dmg.x1 && px0 + 4u > dmg.x0) {
+#else
     if (py < cfg.target_height && px0 < cfg.target_width) {
+#endif
         uint32_t packed[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -2095,6 +2114,16 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
             packed[i] = pack4x8unorm(vec4{fg.x * a_inv, fg.y * a_inv, fg.z * a_inv, fg.w});
         }
         uint8_t *row = output + (size_t)py * out_stride + (size_t)px0 * 4u;
+#ifdef VK_FINE_DAMAGE
+        // the 16-byte store only where the lane's four pixels lie in [x0, x1) and the address allows it; else dword by dword
+        if (px0 >= dmg.x0 && px0 + 4u <= dmg.x1 && ((reinterpret_cast<uintptr_t>(row) & 15u) == 0u)) {
+            *reinterpret_cast<uint4 *>(row) = make_uint4(packed[0], packed[1], packed[2], packed[3]);
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; i++)
+                if (px0 + i >= dmg.x0 && px0 + i < dmg.x1) reinterpret_cast<uint32_t *>(row)[i] = packed[i];
+        }
+#else
         if (px0 + 4u <= cfg.target_width && ((reinterpret_cast<uintptr_t>(row) & 15u) == 0u)) {
             *reinterpret_cast<uint4 *>(row) = make_uint4(packed[0], packed[1], packed[2], packed[3]);
         } else {
@@ -2102,38 +2131,57 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
             for (uint32_t i = 0; i < 4u; i++)
                 if (px0 + i < cfg.target_width) reinterpret_cast<uint32_t *>(row)[i] = packed[i];
         }
+#endif
     }
 }
 
+
+// what a launch passes behind slice_fills: the frame's rectangle (fine_damage.hip), nothing (whole frames)
+#ifdef VK_FINE_DAMAGE
+#define FINE_DAMAGE_ARG , f.damage
+#else
+#define FINE_DAMAGE_ARG
+#endif
 
 template <int AA>
 static void launch_fine_aa(const Frame &f, hipStream_t s, const uint32_t *mask_lut) {
     // MSAA: slice_cap blocks for the slices of long tiles come first (blocks beyond the frame's count leave at once)
     const uint32_t slice_blocks = AA != 0 && f.slice_min_fills != 0u ? f.slice_cap : 0u;
-    dim3 grid(f.cfg.width_in_tiles * f.cfg.height_in_tiles + slice_blocks);
+    // a workgroup per tile of the frame's window (every tile without a damage rectangle): coarse put no other tile into a bucket
+    const TileRect win = damage_window(f.damage);
+    dim3 grid((win.x1 - win.x0) * (win.y1 - win.y0) + slice_blocks);
     uint32_t stride = (uint32_t)f.out_stride;
     constexpr int WAVES_IN_FLIGHT = AA != 0 ? VK_FINE_WAVES_IN_FLIGHT : 4;  // (area AA: one form)
     if (f.brushes)
         hipLaunchKernelGGL((k_fine<AA, true>), grid, dim3(64), 0, s, f.cfg, f.segments, f.ptcl, f.info_bin_data, f.blend_spill, f.output,
                            stride, f.ramps, f.n_ramps, mask_lut, f.atlas, f.atlas_w, f.atlas_h, f.control->work_count, f.tile_order, f.slice_items,
-                           f.slice_counters, f.cov, slice_blocks, f.slice_fills);
+                           f.slice_counters, f.cov, slice_blocks, f.slice_fills FINE_DAMAGE_ARG);
     else if (WAVES_IN_FLIGHT != 4 && !f.flatten_side_by_side)  // (frames in flight)
             hipLaunchKernelGGL((k_fine<AA, false, WAVES_IN_FLIGHT>), grid, dim3(64), 0, s, f.cfg, f.segments, f.ptcl, f.info_bin_data, f.blend_spill, f.output,
                                stride, f.ramps, f.n_ramps, mask_lut, f.atlas, f.atlas_w, f.atlas_h, f.control->work_count, f.tile_order, f.slice_items,
-                               f.slice_counters, f.cov, slice_blocks, f.slice_fills);
+                               f.slice_counters, f.cov, slice_blocks, f.slice_fills FINE_DAMAGE_ARG);
     else
         hipLaunchKernelGGL((k_fine<AA, false>), grid, dim3(64), 0, s, f.cfg, f.segments, f.ptcl, f.info_bin_data, f.blend_spill, f.output,
                            stride, f.ramps, f.n_ramps, mask_lut, f.atlas, f.atlas_w, f.atlas_h, f.control->work_count, f.tile_order, f.slice_items,
-                           f.slice_counters, f.cov, slice_blocks, f.slice_fills);
+                           f.slice_counters, f.cov, slice_blocks, f.slice_fills FINE_DAMAGE_ARG);
 }
 
+#ifdef VK_FINE_DAMAGE
+void launch_fine_damage(const Frame &f, hipStream_t s) {
+#else
 void launch_fine(const Frame &f, hipStream_t s) {
-    if (f.cfg.width_in_tiles * f.cfg.height_in_tiles == 0) return;
+    if (f.cfg.width_in_tiles * f.cfg.height_in_tiles == 0 || empty(f.damage)) return;
+    if (f.damaged) {  // (the kernels that know a rectangle: fine_damage.hip)
+        launch_fine_damage(f, s);
+        return;
+    }
+#endif
     if (f.aa == 0) launch_fine_aa<0>(f, s, f.mask_lut8);
     else if (f.aa == 1) launch_fine_aa<1>(f, s, f.mask_lut8);
     else launch_fine_aa<2>(f, s, f.mask_lut16);
 }
 
+#ifndef VK_FINE_DAMAGE
 // Test seam (vello_hip_stage_constant)
 uint32_t fine_window_words() { return FINE_WINDOW_WORDS; }
 uint32_t fine_batch_fills() { return MS_BATCH_FILLS; }
@@ -2141,5 +2189,6 @@ uint32_t fine_batch_segments() { return MS_BATCH_SEGMENTS; }
 uint32_t fine_item_cap() { return MS_ITEM_CAP; }
 uint32_t fine_simple_records() { return MS_SIMPLE_RECORDS; }
 uint32_t fine_prefetch_reach() { return FINE_PREFETCH_REACH; }
+#endif
 
 }  // namespace vk

@@ -50,6 +50,13 @@ int configure(vello_hip_ctx *c, const SceneSlot &sc, const vello_hip_render_para
     return 0;
 }
 
+// R of a frame of these parameters enqueued now: the context's damage rectangle cut to the target (off: the whole target)
+PixelRect damage_of(const vello_hip_ctx *c, const vello_hip_render_params *p) {
+    if (!c->has_damage) return PixelRect{0u, 0u, p->width, p->height};
+    const auto cut = [](uint32_t v, uint32_t hi) { return v < hi ? v : hi; };
+    return PixelRect{cut(c->damage[0], p->width), cut(c->damage[1], p->height), cut(c->damage[2], p->width), cut(c->damage[3], p->height)};
+}
+
 // k_front's grid-barrier counter (Lane::front_sync) only ever grows, and the host keeps its value: a launch's barriers wait for
 // sync_base + k * (its workgroups).  The two must never drift apart: if a launch is rejected the device never adds, if a
 // barrier's spin bound trips the workgroups stop waiting -- either way the counter goes back to zero on the lane's stream, behind
@@ -77,7 +84,9 @@ void learn_from_frame(SceneSlot &sc, const Control &ctl, const Lane &l) {
     sc.heavy_curves = (int64_t)ctl.heavy_count[0];
     sc.heavy_strokes = (int64_t)ctl.heavy_count[1];
     sc.soup_lines = (int64_t)ctl.bump.lines;
-    if (l.slices_on && (int64_t)ctl.slice_items > sc.slice_demand) sc.slice_demand = (int64_t)ctl.slice_items;
+    // (a damaged frame cut only its window's tiles into slices: its count says nothing about the whole frame, and must not turn
+    // "unknown" into a small number that costs the next whole frame its slice blocks)
+    if (l.slices_on && !l.frame_damaged && (int64_t)ctl.slice_items > sc.slice_demand) sc.slice_demand = (int64_t)ctl.slice_items;
 }
 
 // bump.failed of ONE lane's latest frame -> error code.  Failures are per frame: vello_hip_render judges the lane that
@@ -329,6 +338,10 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
     f.brushes = sc.brushes || c->force_brushes;
     f.no_cull = (c->debug_flags & VELLO_HIP_DEBUG_NO_CULL) != 0u;
     f.viewport_cull = c->viewport_cull;
+    // the damage rectangle, cut to THIS frame's target (off: the whole target)
+    f.damage = damage_of(c, p);
+    f.damaged = f.damage.x0 != 0u || f.damage.y0 != 0u || f.damage.x1 != p->width || f.damage.y1 != p->height;
+    l.frame_damaged = f.damaged;
     f.sequential_clip = (c->debug_flags & VELLO_HIP_DEBUG_SEQ_CLIP) != 0u;
     f.stroke_kernel_min_lines = (c->debug_flags & VELLO_HIP_DEBUG_STROKE_KERNEL) != 0u ? 0u : FLATTEN_STROKE_KERNEL_MIN_LINES;
     f.path_count_small = sc.soup_lines >= 0 && sc.soup_lines < PATH_COUNT_SMALL_MAX_LINES;
@@ -830,7 +843,7 @@ int vello_hip_sync_frame(vello_hip_ctx *c, uint32_t age) {
     HIP_TRY(c, hipStreamSynchronize(l.stream));
     // (once per scene: what flatten counted, so that later frames can leave out a launch that would exit at once)
     SceneSlot &sc = slot_of(c, l);
-    if (l.used && l.flatten_ran && l.zero_region.ptr && l.frame_generation == sc.generation && (sc.stroke_lines < 0 || (l.slices_on && sc.slice_demand < 0))) {
+    if (l.used && l.flatten_ran && l.zero_region.ptr && l.frame_generation == sc.generation && (sc.stroke_lines < 0 || (l.slices_on && !l.frame_damaged && sc.slice_demand < 0))) {
         Control ctl;
         HIP_TRY(c, hipMemcpy(&ctl, l.zero_region.ptr, sizeof ctl, hipMemcpyDeviceToHost));
         if (ctl.bump.failed == 0u) learn_from_frame(sc, ctl, l);
@@ -893,6 +906,25 @@ int vello_hip_set_view_transform(vello_hip_ctx *c, const float view[6]) {
     return VELLO_HIP_OK;
 }
 
+// As the two switches above: a frame takes the rectangle when it is prepared (Frame::damage, cut to that frame's target, travels to
+// k_coarse and k_fine by value), so frames already enqueued keep theirs.  The only refusal is made here, where no frame is at stake:
+// the rotation stays where it was.  What the engine remembers of a scene's earlier frames is not taught by a damaged frame where it
+// would differ from a whole frame's (learn_from_frame).
+int vello_hip_set_damage_rect(vello_hip_ctx *c, const uint32_t rect[4]) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    if (!rect) {
+        c->has_damage = false;
+        return VELLO_HIP_OK;
+    }
+    if (rect[0] > rect[2] || rect[1] > rect[3]) {
+        c->last_error = "set_damage_rect: the rectangle is x0 y0 x1 y1 with x0 <= x1 and y0 <= y1 (half open; an empty one is legal)";
+        return VELLO_HIP_E_INVALID;
+    }
+    c->has_damage = true;
+    for (int k = 0; k < 4; k++) c->damage[k] = rect[k];
+    return VELLO_HIP_OK;
+}
+
 int vello_hip_render(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                      const vello_hip_render_params *params, const uint32_t *ramps, uint32_t n_ramps, void *out_rgba8, size_t out_stride,
                      int out_is_device, vello_hip_bump *bump_out) {
@@ -920,9 +952,13 @@ int vello_hip_render(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, c
     }
     if (sync_r) return sync_r;
     if (out_rgba8 && !out_is_device) {
-        size_t row = (size_t)params->width * 4u;
-        HIP_TRY(c, hipMemcpy2D(out_rgba8, row_stride(params, out_stride), c->lanes[c->last_lane].buf[VELLO_HIP_BUF_OUTPUT].ptr, row, row, params->height,
-                               hipMemcpyDeviceToHost));
+        // R's rows and columns only (the whole target when no damage rectangle is set): the rest of the caller's memory stays as it is
+        const PixelRect d = damage_of(c, params);
+        const size_t row = (size_t)params->width * 4u, at = (size_t)d.x0 * 4u;
+        if (!empty(d))
+            HIP_TRY(c, hipMemcpy2D((uint8_t *)out_rgba8 + (size_t)d.y0 * row_stride(params, out_stride) + at, row_stride(params, out_stride),
+                                   (const uint8_t *)c->lanes[c->last_lane].buf[VELLO_HIP_BUF_OUTPUT].ptr + (size_t)d.y0 * row + at, row,
+                                   (size_t)(d.x1 - d.x0) * 4u, d.y1 - d.y0, hipMemcpyDeviceToHost));
     }
     return VELLO_HIP_OK;
 }

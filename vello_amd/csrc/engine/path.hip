@@ -696,8 +696,15 @@ __global__ void __launch_bounds__(256) k_backdrop(Config cfg, const Bump *__rest
 __global__ void __launch_bounds__(256) k_path_tiling(Config cfg, Bump *bump, const SegmentCount *__restrict__ seg_counts,
                                                      const LineSoup *__restrict__ lines, const Path *__restrict__ paths,
                                                      const Tile *__restrict__ tiles, Segment *__restrict__ segments, uint32_t *ptcl) {
-    if (bump->failed != 0u) {  // path_tiling_setup.wgsl:21-25
-        if (blockIdx.x == 0 && threadIdx.x == 0) ptcl[0] = ~0u;
+    // path_tiling_setup.wgsl:21-25.  The segment pool is judged by what coarse handed out: a frame with a damage rectangle asks for
+    // the segments of its window's tiles only.  (Whole frames: bump.segments <= bump.seg_counts <= the seg_counts pool, and the
+    // segment pool is at least as large unless vello_hip_create was told otherwise -- the second test never decides.)
+    const bool seg_overflow = bump->segments > cfg.segments_size;
+    if (bump->failed != 0u || seg_overflow) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            if (seg_overflow) atomicOr(&bump->failed, STAGE_COARSE);
+            ptcl[0] = ~0u;
+        }
         return;
     }
     const float TILE_SCALE = 0.0625f;
@@ -857,6 +864,10 @@ void launch_path_tiling(const Frame &f, hipStream_t s) {
 #ifndef VK_PT_GRID_IN_FLIGHT
 #define VK_PT_GRID_IN_FLIGHT 2048u  // (sweep constant: the grid's cap with frames in flight)
 #endif
+    // A damage rectangle needs nothing here: a crossing whose tile got no segment slice from coarse -- a tile outside the frame's
+    // window -- still finds the tile's COUNT in segment_count_or_ix and is dropped by the kernel's test of it.  An empty window
+    // gave no tile a slice: no launch.
+    if (empty(f.damage)) return;
     uint32_t grid = clamp_grid(f.cfg.seg_counts_size, PATH_TILING_WG, f.flatten_side_by_side ? 2048u : VK_PT_GRID_IN_FLIGHT);
     hipLaunchKernelGGL(k_path_tiling, dim3(grid), dim3(256), 0, s, f.cfg, f.bump(), f.seg_counts, f.lines, f.paths, f.tiles,
                        f.segments, f.ptcl);

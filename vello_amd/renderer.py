@@ -36,11 +36,24 @@ PATH_DATA_SCENE, PATH_DATA_DEVICE = 0xFFFFFFFF, 0xFFFFFFFE  # VELLO_HIP_PATH_DAT
 
 class RenderParams:
     """`view` (an Affine, or six floats [m0 m1 m2 m3 t0 t1]; default None) is a view transform for this frame only: the engine
-    composes it in front of every transform of the scene (vello_hip_set_view_transform)."""
+    composes it in front of every transform of the scene (vello_hip_set_view_transform).  `damage` ((x0, y0, x1, y1) in pixels,
+    half open; default None) is a damage rectangle for this frame only: the frame writes only those pixels of the target
+    (vello_hip_set_damage_rect)."""
 
-    def __init__(self, base_color, width, height, antialiasing_method=AaConfig.Area, view=None):
+    def __init__(self, base_color, width, height, antialiasing_method=AaConfig.Area, view=None, damage=None):
         self.base_color, self.width, self.height, self.antialiasing_method = base_color, width, height, antialiasing_method
         self.view = view
+        self.damage = damage
+
+
+def _damage_words(rect):
+    """x0 y0 x1 y1 as the four u32 of vello_hip_set_damage_rect (None: the option off)."""
+    if rect is None:
+        return None
+    rect = tuple(rect)
+    if len(rect) != 4 or any(int(v) < 0 or int(v) > 0xFFFFFFFF for v in rect):
+        raise ValueError("a damage rectangle is (x0, y0, x1, y1) in pixels, half open")
+    return (ctypes.c_uint32 * 4)(*[int(v) for v in rect])
 
 
 def _view_floats(view):
@@ -265,9 +278,18 @@ class Renderer:
             import torch
 
             src_stream, relay = _source_stream(torch.cuda.current_stream())
-        r = self._lib.vh_renderer_render_to_texture_view(self._h, scene._h, ptr, stride, 1 if is_dev else 0, params.width, params.height,
-                                                         params.base_color._ptr(), int(params.antialiasing_method), src_stream,
-                                                         _view_floats(getattr(params, "view", None)))
+        # a damage rectangle holds for this frame only: set on the engine before the call, cleared after it (as the view is)
+        damage = _damage_words(getattr(params, "damage", None))
+        engine = self._lib.vh_renderer_engine(self._h)
+        if damage is not None and self._lib.vello_hip_set_damage_rect(engine, damage) != 0:
+            raise VelloHipError(f"render_to_texture: {self._lib.vello_hip_last_error(engine).decode()}")
+        try:
+            r = self._lib.vh_renderer_render_to_texture_view(self._h, scene._h, ptr, stride, 1 if is_dev else 0, params.width, params.height,
+                                                             params.base_color._ptr(), int(params.antialiasing_method), src_stream,
+                                                             _view_floats(getattr(params, "view", None)))
+        finally:
+            if damage is not None:
+                self._lib.vello_hip_set_damage_rect(engine, None)
         if relay is not None:
             relay[0].wait_stream(relay[1])
         if r != 0:
@@ -829,6 +851,11 @@ class Engine:
         of the soup (bump["lines"] counts the rest); path boxes and everything behind the soup, the image included, are unchanged.
         Applies to frames enqueued after the call."""
         self._check(self._lib.vello_hip_set_viewport_cull(self._h, 1 if enabled else 0), "set_viewport_cull")
+
+    def set_damage_rect(self, rect=None):
+        """vello_hip_set_damage_rect: frames enqueued from here on render only the tiles that `rect` ((x0, y0, x1, y1) in pixels,
+        half open) touches and write only its pixels; everything ahead of coarse is the whole frame's.  None: whole frames."""
+        self._check(self._lib.vello_hip_set_damage_rect(self._h, _damage_words(rect)), "set_damage_rect")
 
     def set_view_transform(self, view=None):
         """vello_hip_set_view_transform: frames enqueued from here on are rendered as if every transform T of the scene were
