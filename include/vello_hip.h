@@ -360,6 +360,51 @@ int vello_hip_set_damage_rect(vello_hip_ctx *ctx, const uint32_t rect[4] /* x0 y
 int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                                        const vello_hip_render_params *params, const float view[6] /* nullable */,
                                        vello_hip_capacities *out);
+/* Stroke scale for the frames that follow (default: none): non-scaling strokes under a view.  `stroke` is (s, m): a frame enqueued
+ * while it is set is rendered as if every stroke width of the scene's style stream had been multiplied by s and raised to at
+ * least m -- what a host does by patching the widths and packing and uploading the scene again, without any of the three.  A
+ * caller whose view zooms by z passes s = 1 / z for strokes that keep their width on screen (SVG's vector-effect:
+ * non-scaling-stroke) and m = hairline / z for strokes that never fall below a hairline.
+ *   1. THE FRAME'S STYLE WORDS.  The style stream is the entries e < n_styles = (scene_words - style_base) / 2; entry e is
+ *      flags = scene[style_base + 2e] and w = scene[style_base + 2e + 1] as f32.  The flags word is copied verbatim.  The width word
+ *      becomes w' = (x < m ? m : x) with x = fl(w * s) -- one f32 multiply, IEEE-rounded, and one compare -- iff
+ *      (flags & STYLE_FLAGS_STYLE) != 0 and w > 0.0f.  Every other width word is a bit copy: fills, and strokes of width 0, of
+ *      negative width or of NaN width (payloads and signed zeros arrive as they were).  The zero-width stroke that encodes an empty
+ *      clip (scene.rs:179-183) therefore stays empty whatever m is.  s and m are in the path's own units, ahead of its transform,
+ *      as the width is.
+ *   2. WHAT SUCH A FRAME IS.  Bit for bit in every buffer and counter, the frame the same entry point would enqueue had the scene
+ *      carried these words in its style stream (the line soup and the segment slices as multisets, as everywhere): under a view,
+ *      viewport culling, a damage rectangle and a morph, with frames in flight, with and without the scene index, in the
+ *      small-scene launches and without them, and with every kernel choice of the debug flags.
+ *   3. STYLE INDEX -1.  A segment met before any STYLE marker keeps reading the two words BELOW the scene's own style stream,
+ *      unscaled -- the rule the view has for transform -1.
+ *   4. The scene is never modified: VELLO_HIP_BUF_SCENE shows the uploaded, composed or retained bytes, VELLO_HIP_BUF_CONFIG the
+ *      scene's own layout.  The scene index stays valid: vello_hip_scene_index_builds does not move.
+ *   5. Applies to frames enqueued after the call on every entry point that renders (render, render_frame, render_resident,
+ *      render_resident_morphed, render_instances[_painted], render_retained[_painted], and run_stages when the range holds
+ *      FLATTEN -- otherwise run_stages goes on from the lane's buffers as they are) and on all in-flight buffer sets; frames
+ *      already enqueued keep the setting they were enqueued with: four frames in flight may carry four scales.  For composed and
+ *      retained frames the composed or retained style stream is read on the device; the host never sees those bytes.
+ *   6. A non-null setting always runs the kernel; (1, 0) gives the off state's buffers and counters on a scene of finite widths.
+ *      NULL restores the off state bit for bit: frames without the setting run exactly the launches they run without this call.
+ *   7. VELLO_HIP_E_INVALID, with vello_hip_last_error naming the rule and nothing changed (the setting, the rotation, the frames in
+ *      flight), for a null context (no message: there is no context to hold one), for s that is NaN, infinite or <= 0, and for m
+ *      that is NaN, infinite or < 0.  A scene whose packed bytes and copies together reach 2^32 words is refused with
+ *      VELLO_HIP_E_INVALID when a frame with the setting is enqueued, the rotation left where it was.
+ *   8. vello_hip_pick and vello_hip_pick_rect answer against the scaled strokes: they read the frame's soup and path boxes.
+ *   9. With vello_hip_set_auto_grow the blocking vello_hip_render sizes the pools with vello_hip_estimate_capacities_styled and the
+ *      context's setting.
+ * The frame's style words are written by one small kernel (k_style_widths, a lane per entry) at the head of every frame that has
+ * the setting, into a per-frame copy behind the scene's bytes; nothing crosses PCIe.
+ * OUT OF SCOPE: per-style widths or factors from host or device memory (the same copy, another source); changing caps, joins,
+ * miter limits or fill versus stroke (the scene index depends on the flags); a width in screen space for scenes whose transforms
+ * differ in scale (s and m are applied ahead of each path's own transform). */
+int vello_hip_set_stroke_scale(vello_hip_ctx *ctx, const float stroke[2] /* scale, min_width; nullable: off (default) */);
+/* vello_hip_estimate_capacities_view with rule 1 of vello_hip_set_stroke_scale applied to every width the estimator reads; equal to
+ * it for stroke == NULL.  VELLO_HIP_E_INVALID for a `stroke` that vello_hip_set_stroke_scale refuses. */
+int vello_hip_estimate_capacities_styled(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                                         const vello_hip_render_params *params, const float view[6] /* nullable */,
+                                         const float stroke[2] /* nullable */, vello_hip_capacities *out);
 
 /* Scene instances: the resident scene as a library of fragments, a frame as a list of (fragment, transform) pairs -- what a host
  * builds with Scene::append(&fragment, Some(transform)) per pair (vello_encoding/src/encoding.rs:95-152), composed on the GPU. */

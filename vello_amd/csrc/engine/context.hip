@@ -183,13 +183,17 @@ int presize_pools(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, cons
     uint64_t n_seg = 0;
     for (size_t i = 0; i < n_tags; i++) n_seg += (tags[i] & 3u) != 0u;
     const uint64_t n_tiles = (uint64_t)((params->width + 15u) / 16u) * ((params->height + 15u) / 16u);
-    // (the cheap test stands for content at the scale it was encoded at: under a view the estimator is always asked)
-    if (!c->has_view && 4u * n_seg <= c->caps.lines && 8u * n_seg <= c->caps.seg_counts && 4u * n_seg + 8u * layout->n_paths <= c->caps.tiles &&
+    // (the cheap test stands for content at the scale and the stroke widths it was encoded with: under a view or a stroke scale the
+    // estimator is always asked)
+    if (!c->has_view && !c->has_stroke && 4u * n_seg <= c->caps.lines && 8u * n_seg <= c->caps.seg_counts && 4u * n_seg + 8u * layout->n_paths <= c->caps.tiles &&
         160u * n_tiles + 16u * n_seg <= c->caps.ptcl)
         return VELLO_HIP_OK;
     vello_hip_capacities est;
     const float view[6] = {c->view.m0, c->view.m1, c->view.m2, c->view.m3, c->view.t0, c->view.t1};
-    if (vello_hip_estimate_capacities_view(scene, scene_len, layout, params, c->has_view ? view : nullptr, &est) != VELLO_HIP_OK) return VELLO_HIP_OK;
+    const float stroke[2] = {c->stroke_scale, c->stroke_min};
+    if (vello_hip_estimate_capacities_styled(scene, scene_len, layout, params, c->has_view ? view : nullptr, c->has_stroke ? stroke : nullptr, &est) !=
+        VELLO_HIP_OK)
+        return VELLO_HIP_OK;
     vello_hip_capacities d = c->caps;
     bool grew = false;
     auto want = [&](uint32_t &cap, uint32_t need) {

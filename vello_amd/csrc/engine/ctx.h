@@ -84,6 +84,12 @@ struct SceneSlot {
     // (ensure_morph_room), not by the upload: scenes that are never morphed pay nothing.
     size_t pd_at = 0;
     uint32_t pd_sets = 0, pd_set_words = 0;
+    // The style words of frames with a stroke scale (vello_hip_set_stroke_scale, Frame::st_base): `st_sets` copies of
+    // (n_styles + 1) * 2 words each -- slot -1 first -- from word `st_at` of the scene's allocation: behind the transform copies, in
+    // the same tail (view_cap_bytes covers both), on an even word, so that a copy is 8-byte aligned where the scene's stream is.
+    // A copy per lane in the shared and the retained slot, one in a lane's private slot, as the transform copies.
+    size_t st_at = 0;
+    uint32_t st_sets = 0, st_set_words = 0;
     bool i16_segments = false;  // a segment tag without PATH_TAG_F32 is present (found by load_slot from the host bytes): no blends
 };
 constexpr uint32_t PD_SLACK_WORDS = 8u;  // (a cubic's four points: what read_path_segment reads from a tag's offset on)
@@ -241,6 +247,8 @@ struct vello_hip_ctx {
     bool viewport_cull = false;  // vello_hip_set_viewport_cull: copied into every Frame when it is prepared
     bool has_view = false;       // vello_hip_set_view_transform: likewise
     vk::Xform view{1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
+    bool has_stroke = false;     // vello_hip_set_stroke_scale: likewise
+    float stroke_scale = 1.0f, stroke_min = 0.0f;
     bool has_damage = false;     // vello_hip_set_damage_rect: likewise; cut to the frame's target by prepare_frame (Frame::damage)
     uint32_t damage[4] = {0u, 0u, 0u, 0u};  // x0 y0 x1 y1 as the caller gave them (x0 <= x1, y0 <= y1)
     hipStream_t copy_stream = nullptr;  // vello_hip_gather_frames: this context's peer copy
@@ -307,6 +315,7 @@ int check_target(vello_hip_ctx *c, const vello_hip_render_params *p, const void 
 int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
 int paint_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
 int morph_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
+int style_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
 int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, void *out_device, size_t out_stride, Frame &f, bool upload_cfg);
 int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int last);
 // scenes.hip
@@ -341,8 +350,8 @@ constexpr auto no_step = [](Lane &) { return 0; };
 //   staged(l)              what else may refuse the frame, asked after the view's pre-check and before prepare_frame
 //   enqueue(l)             what the lane's stream gets ahead of the stages
 // The view's pre-check (view_base) comes before the rotation moves, for the slot the frame will read -- not for a shared slot that
-// holds no scene: prepare_frame refuses that frame itself.  A composed slot whose frame prepare_frame refuses holds no scene: its
-// bytes were never written.
+// holds no scene: prepare_frame refuses that frame itself.  The stroke scale's (style_base) likewise.  A composed slot whose frame
+// prepare_frame refuses holds no scene: its bytes were never written.
 template <class SetUp, class Staged, class Enqueue>
 int enter_frame(vello_hip_ctx *c, const vello_hip_render_params *params, void *out_device, size_t out_stride, bool rotate_first, int last,
                 SetUp set_up, Staged staged, Enqueue enqueue) {
@@ -364,6 +373,8 @@ int enter_frame(vello_hip_ctx *c, const vello_hip_render_params *params, void *o
     if ((c->has_view || l.which == LaneScene::Retained) && (l.which != LaneScene::Shared || c->shared.resident) &&
         (r = view_base(c, slot_of(c, l), l, xf_base)))
         return r;
+    // (the stroke scale's pre-check: asked for its refusal only -- prepare_frame picks the base)
+    if (uint32_t probe; c->has_stroke && (l.which != LaneScene::Shared || c->shared.resident) && (r = style_base(c, slot_of(c, l), l, probe))) return r;
     if ((r = staged(l))) return r;
     const auto rotate = [&] {
         c->next_lane = (li + 1u) % c->n_active;

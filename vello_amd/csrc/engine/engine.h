@@ -207,6 +207,16 @@ struct Frame {
     uint32_t pd_mode;
     float pd_t;
     hipStream_t pd_stream;
+    // The style words flatten reads: entry e lies at scene[(u32)(st_base + e * 2)] (flags, then the stroke width).  The scene's own
+    // stream (st_base == cfg.layout.style_base) for every frame but one with a stroke scale (vello_hip_set_stroke_scale): there it
+    // is the lane's copy behind the scene's bytes and the transform copies, which k_style_widths fills at the head of the frame --
+    // slot -1 holds the two words below the stream verbatim, slot e the flags verbatim and the width under the rule of
+    // StyleWidthArgs.  The readers are handed a Config whose layout.style_base is st_base (xf_config) and are the same code
+    // whether a scale is set or not.  The pathtag scan keeps the scene's own Config: it judges the stream's length against
+    // n_scene_words, and reads flags only.
+    uint32_t st_base;
+    bool has_stroke;
+    float stroke_scale, stroke_min;
     Control *control;
     uint32_t *heavy_list;   // flatten: tag indices that need the Euler-spiral / stroker path
     uint32_t *arc_items;    // flatten: 16 words per round join / cap arc that a stroke workgroup leaves to the heavy code
@@ -273,16 +283,20 @@ struct Frame {
 
 // the Config of the kernels that read transforms (flatten's, the draw stage's): the frame's, with the transform words' base -- and
 // the draw-data words' base, which the draw stage reads through the same Config (an unpainted frame's: the scene's own), and the
-// path-data words' base, which flatten reads through it (an unmorphed frame's: the scene's own)
+// path-data words' base, which flatten reads through it (an unmorphed frame's: the scene's own), and the style words' base, which
+// flatten reads through it (a frame's without a stroke scale: the scene's own)
 inline Config xf_config(const Frame &f) {
     Config c = f.cfg;
     c.layout.transform_base = f.xf_base;
     c.layout.draw_data_base = f.dd_base;
     c.layout.path_data_base = f.pd_base;
+    c.layout.style_base = f.st_base;
     return c;
 }
 // whether the frame's path-data words are the lane's copy (a morphed frame, or vello_hip_run_stages after one)
 inline bool morphed(const Frame &f) { return f.pd_base != f.cfg.layout.path_data_base; }
+// whether the frame's style words are the lane's copy (a frame with a stroke scale)
+inline bool styled(const Frame &f) { return f.st_base != f.cfg.layout.style_base; }
 // the Config of k_coarse_prep, which reads draw data and no transforms: the frame's, with the draw-data words' base
 inline Config dd_config(const Frame &f) {
     Config c = f.cfg;
@@ -339,6 +353,20 @@ struct PathBlendArgs {
 };
 // fills the path-data words of a morphed frame (Frame::pd_a is set)
 void launch_path_blend(const Frame &f, hipStream_t s);
+// k_style_widths (scene_ops.hip): what it is handed by value.  Entry e of `out` is the scene's style entry e -- (flags, width) --
+// with the flags verbatim and the width w replaced by max(fl(w * scale), min_width) iff the entry is a stroke
+// (flags & STYLE_FLAGS_STYLE) and w > 0; every other width is a bit copy (rule 1 of vello_hip_set_stroke_scale).  The two words in
+// front of `out` are slot -1: the two words below the scene's stream verbatim (zeros when the scene has no two words there).  The
+// host picks the access width: 8-byte accesses when stream and copy are both 8-byte aligned, dword accesses otherwise
+// (launch_style_widths).
+struct StyleWidthArgs {
+    const uint32_t *scene;  // the frame's scene: uploaded, composed or retained
+    uint32_t *out;          // entry 0 of the lane's copy (slot -1 lies two words in front)
+    uint32_t style_base, n_styles;
+    float scale, min_width;
+};
+// fills the style words of a frame with a stroke scale (Frame::has_stroke)
+void launch_style_widths(const Frame &f, hipStream_t s);
 
 void launch_pathtag_scan(const Frame &f, hipStream_t s);
 // k_frame_begin (scan.hip), an indexed frame's first launch: the zero fill of the lane's zero region, the path boxes from the

@@ -92,9 +92,15 @@ struct PathAcc {
 }  // namespace
 
 // `view` (nullable): vello_hip_set_view_transform's V, composed with every entry of the transform stream where it is read
-extern "C" int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
-                                                  const vello_hip_render_params *params, const float view[6], vello_hip_capacities *out) {
+// `stroke` (nullable): vello_hip_set_stroke_scale's (scale, min_width), applied by its rule 1 to every width where it is read
+extern "C" int vello_hip_estimate_capacities_styled(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                                                    const vello_hip_render_params *params, const float view[6], const float stroke[2],
+                                                    vello_hip_capacities *out) {
     if ((!scene && scene_len) || !layout || !params || !out || (scene_len & 3u)) return VELLO_HIP_E_INVALID;
+    if (stroke) {  // as vello_hip_set_stroke_scale: a finite scale > 0, a finite minimum >= 0
+        const float s = stroke[0], m = stroke[1];
+        if (!(s - s == 0.0f) || !(s > 0.0f) || !(m - m == 0.0f) || !(m >= 0.0f)) return VELLO_HIP_E_INVALID;
+    }
     if (view)
         for (int k = 0; k < 6; k++)
             if (!(view[k] - view[k] == 0.0f)) return VELLO_HIP_E_INVALID;  // NaN or infinity, as vello_hip_set_view_transform
@@ -272,6 +278,11 @@ extern "C" int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t s
                 float wd;
                 std::memcpy(&wd, &w[L.style_base + n_style_seen * 2u + 1u], 4);
                 is_stroke = (style_flags & vk::STYLE_FLAGS_STYLE) != 0u;
+                if (stroke && is_stroke && wd > 0.0f) {
+                    // the width word the frame's flatten reads, as k_style_widths (scene_ops.hip) computes it: one f32 product
+                    const float x = wd * stroke[0];
+                    wd = x < stroke[1] ? stroke[1] : x;
+                }
                 width = is_stroke ? std::fabs((double)wd) : 0.0;
             }
             n_style_seen++;
@@ -298,6 +309,11 @@ extern "C" int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t s
     out->ptcl = cap32(128u * n_tiles + 2u * n_segments + 7u * T.ptcl_pairs + 4096u);
     out->blend_spill = 0u;  // clip depth is not visible in the path streams: left to the caller / auto-grow
     return VELLO_HIP_OK;
+}
+
+extern "C" int vello_hip_estimate_capacities_view(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
+                                                  const vello_hip_render_params *params, const float view[6], vello_hip_capacities *out) {
+    return vello_hip_estimate_capacities_styled(scene, scene_len, layout, params, view, nullptr, out);
 }
 
 extern "C" int vello_hip_estimate_capacities(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,

@@ -2128,9 +2128,11 @@ uint32_t launch_front(const Frame &f, hipStream_t s, uint32_t stages, bool with_
     // A frame whose transform words are a composed copy (one with a view, Frame::has_view, or of the retained instance list,
     // Frame::retained): the pathtag scan judges the tag stream against the scene's own layout, the stages behind it read the
     // composed words through theirs (xf_config) -- two launches of the same kernel, cut behind the scan.  Likewise a frame whose
-    // path-data words are the lane's copy (a morphed frame): the scan judges lengths against the scene's own layout.
+    // path-data words are the lane's copy (a morphed frame): the scan judges lengths against the scene's own layout.  Likewise a
+    // frame whose style words are the lane's copy (one with a stroke scale): the scan judges the style stream's length from
+    // the scene's own base.
     const uint32_t scan_part = FRONT_ZERO | FRONT_PATHTAG;
-    if ((f.has_view || f.retained || morphed(f)) && (stages & FRONT_PATHTAG) != 0u && (stages & ~scan_part) != 0u) {
+    if ((f.has_view || f.retained || morphed(f) || styled(f)) && (stages & FRONT_PATHTAG) != 0u && (stages & ~scan_part) != 0u) {
         FrontArgs a0 = a, a1 = a;
         a0.stages = stages & scan_part;
         a1.stages = stages & ~scan_part;

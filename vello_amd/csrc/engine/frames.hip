@@ -167,6 +167,20 @@ int morph_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &b
     return 0;
 }
 
+// Where entry 0 of lane l's copy of the style words lies, in words from the scene's start (SceneSlot::st_at; two words into the
+// copy: slot -1 comes first): what a frame with a stroke scale reads in the stream's place.  VELLO_HIP_E_INVALID for a scene so
+// large that the copy is out of a u32 offset's reach; asked before the rotation moves, as view_base is.
+int style_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base) {
+    const size_t set = l.which == LaneScene::Own ? 0u : (size_t)(&l - c->lanes.data());
+    const uint64_t at = (uint64_t)sc.st_at + (uint64_t)set * sc.st_set_words + 2u;
+    if (set >= sc.st_sets || at + sc.st_set_words > 0xffffffffull) {
+        c->last_error = "the scene is too large for a stroke scale (its bytes and copies must lie within 2^32 words of its start)";
+        return VELLO_HIP_E_INVALID;
+    }
+    base = (uint32_t)at;
+    return 0;
+}
+
 // The target contract of include/vello_hip.h (at vello_hip_render_resident).  fine stores dwords at output + y * stride and takes the
 // stride as a u32: a device target that is not 4-aligned, rows that overlap or a stride of 2^32 and more would corrupt silently.
 // Every entry point that takes a target asks before it uploads, rotates or enqueues anything.
@@ -279,6 +293,22 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
         f.pd_mode = l.pd_mode;
         f.pd_t = l.pd_t;
         f.pd_stream = l.pd_stream;
+    }
+    // its style words: the scene's own -- or, with a stroke scale, the lane's copy, which k_style_widths fills at the head of the
+    // frame (a scene without a style entry keeps its own stream: nothing would fill the copy, and no tag reads a style word)
+    f.has_stroke = c->has_stroke;
+    f.stroke_scale = c->stroke_scale;
+    f.stroke_min = c->stroke_min;
+    f.st_base = sc.layout.style_base;
+    if (f.has_stroke) {
+        uint32_t at;
+        if ((r = style_base(c, sc, l, at))) return r;
+        if ((f.n_scene_words - sc.layout.style_base) / STYLE_SIZE_IN_WORDS != 0u) f.st_base = at;
+        // Rule 4 of the contract says what VELLO_HIP_BUF_CONFIG shows behind such a frame: the scene's own layout.  An entry point that
+        // enqueues without the blocking copy (vello_hip_render_resident among them, which marks nothing on its own) would leave
+        // the device copy as an earlier frame or no frame left it, so the frame's Config is marked for sending when the buffer
+        // is next read or written, as the composed, retained and morphed entry points mark theirs.  (f.cfg never carries st_base.)
+        if (!upload_cfg) c->cfg_unsent = true;
     }
     f.control = (Control *)l.zero_region.ptr;
     f.zero_bytes = (uint32_t)sc.zero_bytes;
@@ -455,6 +485,13 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
             HIP_TRY(c, hipEventRecord(f.pose_mark, st));
             HIP_TRY(c, hipStreamWaitEvent(f.pd_stream, f.pose_mark, 0));
         }
+    }
+    // A frame with a stroke scale: its style words first, beside the view's transform words, when the range holds the stage that
+    // reads widths.  (For a composed frame this sits behind k_compose_scene on the lane's stream: the kernel reads the composed
+    // style stream; the retained list's is resident.)
+    if (styled(f) && first <= VELLO_HIP_STAGE_FLATTEN && last >= VELLO_HIP_STAGE_FLATTEN) {
+        launch_style_widths(f, st);
+        HIP_TRY(c, hipGetLastError());
     }
     const uint32_t front_zero = zeroed ? 0u : FRONT_ZERO;
     for (int s = first; s <= last; s++) {
@@ -903,6 +940,31 @@ int vello_hip_set_view_transform(vello_hip_ctx *c, const float view[6]) {
         }
     c->has_view = true;
     c->view = Xform{view[0], view[1], view[2], view[3], view[4], view[5]};
+    return VELLO_HIP_OK;
+}
+
+// As the view: a frame takes the setting when it is prepared (Frame::stroke_scale / stroke_min travel to k_style_widths by value, and
+// the frame's style words are its lane's own copy), so frames already enqueued keep theirs.  Nothing the engine remembers of a
+// scene depends on a width: the scene index holds tags and flags, and what a finished frame teaches (SceneSlot) only picks among
+// kernels and launch shapes that are all correct for any width.  The refusals are made here, where no frame is at stake.
+int vello_hip_set_stroke_scale(vello_hip_ctx *c, const float stroke[2]) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    if (!stroke) {
+        c->has_stroke = false;
+        return VELLO_HIP_OK;
+    }
+    const float s = stroke[0], m = stroke[1];
+    if (!(s - s == 0.0f) || !(s > 0.0f)) {
+        c->last_error = "set_stroke_scale: the scale must be finite and > 0";
+        return VELLO_HIP_E_INVALID;
+    }
+    if (!(m - m == 0.0f) || !(m >= 0.0f)) {
+        c->last_error = "set_stroke_scale: the minimum width must be finite and >= 0";
+        return VELLO_HIP_E_INVALID;
+    }
+    c->has_stroke = true;
+    c->stroke_scale = s;
+    c->stroke_min = m;
     return VELLO_HIP_OK;
 }
 

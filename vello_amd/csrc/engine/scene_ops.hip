@@ -1,5 +1,5 @@
 // Device-side operations on scene data outside the pipeline's stages: atlas copies, the view's transform words, a retained list's
-// per-frame transform and draw-data words, a morphed frame's path-data words, scene composition.
+// per-frame transform and draw-data words, a morphed frame's path-data words, a stroke scale's style words, scene composition.
 #include "engine.h"
 
 namespace vk {
@@ -271,6 +271,64 @@ void launch_path_blend(const Frame &f, hipStream_t s) {
     if (wgs > PATH_BLEND_MAX_WGS) wgs = PATH_BLEND_MAX_WGS;
     if (vec) hipLaunchKernelGGL(k_path_blend<true>, dim3(wgs), dim3(256), 0, s, g);
     else hipLaunchKernelGGL(k_path_blend<false>, dim3(wgs), dim3(256), 0, s, g);
+}
+
+// k_style_widths: the style words of a frame with a stroke scale (vello_hip_set_stroke_scale; the arguments are in engine.h), beside
+// k_view_transforms at the head of the frame, a lane per style entry as that kernel takes a transform entry.  Entry e of `out` -- the
+// lane's copy of the stream, which flatten then reads in the stream's place -- is (flags, w'): the flags verbatim, and
+// w' = max(fl(w * scale), min_width) where the entry is a stroke of positive width, the bits of w everywhere else (a fill, a width
+// of 0, a negative one, a NaN: the comparison w > 0 fails for all of them).  One f32 multiply and one compare; scale and min_width
+// are kernel arguments, so wave-uniform.  VEC: stream and copy are both 8-byte aligned (the host has looked): one dwordx2 load and
+// one dwordx2 store a lane, 512 B of consecutive memory a wave.  !VEC (a style stream that begins on an odd word): two dword loads
+// and two dword stores at a stride of 8 bytes -- the same 512 B a wave.  Workgroup 0's first lane also writes slot -1, the two words
+// in front of `out`: the two words below the scene's stream verbatim, which a segment met before any STYLE marker reads (zeros when
+// the scene has no two words there -- a scene that short has no tags).  No LDS, nothing is shared.
+__device__ __forceinline__ uint32_t style_width_word(uint32_t flags, uint32_t w_bits, float scale, float min_width) {
+    // (a single operation -- nothing to contract -- under the file's discipline all the same: path_blend_word has the reasons)
+#pragma clang fp contract(off)
+    const float w = __uint_as_float(w_bits);
+    if ((flags & STYLE_FLAGS_STYLE) == 0u || !(w > 0.0f)) return w_bits;
+    const float x = w * scale;
+    return __float_as_uint(x < min_width ? min_width : x);
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_style_widths(StyleWidthArgs a) {
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e == 0u) {
+        const bool below = a.style_base >= 2u;
+        a.out[-2] = below ? a.scene[a.style_base - 2u] : 0u;
+        a.out[-1] = below ? a.scene[a.style_base - 1u] : 0u;
+    }
+    if (e >= a.n_styles) return;
+    const uint32_t *src = a.scene + (size_t)a.style_base + (size_t)e * 2u;
+    uint32_t *dst = a.out + (size_t)e * 2u;
+    if (VEC) {
+        const uint64_t v = *reinterpret_cast<const uint64_t *>(src);  // (little endian: the flags are the low word)
+        const uint32_t flags = (uint32_t)v;
+        *reinterpret_cast<uint64_t *>(dst) = (uint64_t)style_width_word(flags, (uint32_t)(v >> 32), a.scale, a.min_width) << 32 | flags;
+    } else {
+        const uint32_t flags = src[0], w = src[1];
+        dst[0] = flags;
+        dst[1] = style_width_word(flags, w, a.scale, a.min_width);
+    }
+}
+
+void launch_style_widths(const Frame &f, hipStream_t s) {
+    StyleWidthArgs a{};
+    a.scene = f.scene;
+    a.out = const_cast<uint32_t *>(f.scene) + f.st_base;  // (slot -1 of the copy: two words in front of st_base)
+    a.style_base = f.cfg.layout.style_base;
+    a.n_styles = (f.n_scene_words - f.cfg.layout.style_base) / STYLE_SIZE_IN_WORDS;
+    a.scale = f.stroke_scale;
+    a.min_width = f.stroke_min;
+    if (a.n_styles == 0u) return;  // (no style entry: no tag reads a style word, slot -1 included)
+    // the access width, decided here: the scene's allocation is 256-byte aligned, so word parities are address parities -- the copy
+    // begins on an even word (size_slot), the stream where the scene's layout puts it
+    const bool vec = ((reinterpret_cast<uintptr_t>(a.scene + a.style_base) | reinterpret_cast<uintptr_t>(a.out)) & 7u) == 0u;
+    const uint32_t wgs = (a.n_styles + 255u) / 256u;
+    if (vec) hipLaunchKernelGGL(k_style_widths<true>, dim3(wgs), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_style_widths<false>, dim3(wgs), dim3(256), 0, s, a);
 }
 
 // k_compose_scene: a frame's packed scene written from instances of the library's fragments (vello_hip_render_instances; the contract is

@@ -57,18 +57,25 @@ int size_slot(vello_hip_ctx *c, SceneSlot &sc, const vello_hip_layout &L, size_t
     const uint32_t sets = &sc == &c->shared || &sc == &c->retained ? MAX_LANES : 1u;
     // ... and, the retained slot only, behind those a copy per lane of the draw-data stream for painted frames (SceneSlot::dd_at) --
     // unless the copies would lie beyond a u32 word offset from the scene's start: such a list takes no paints and gets no room
-    const size_t xf_tail_words = (size_t)set_words * sets;
+    // ... and, behind those, the style words of frames with a stroke scale (SceneSlot::st_at): as many copies, each the stream's
+    // entries and slot -1 in front; from an even word (the transform copies are whole entries of six words from a 16-byte boundary)
+    const size_t st_set_words = ((scene_len / 4u - L.style_base) / STYLE_SIZE_IN_WORDS + 1u) * STYLE_SIZE_IN_WORDS;
+    const size_t xf_tail_words = ((size_t)set_words * sets + 1u) & ~(size_t)1u;
+    const size_t st_tail_words = st_set_words * sets;
     const uint32_t dd_words = L.transform_base - L.draw_data_base;
     uint32_t dd_sets = 0u;
     if (&sc == &c->retained) {
         const size_t visible = sc.scene.size > scene_len + 64 ? sc.scene.size : scene_len + 64;  // (what ensure_scene settles on)
-        const uint64_t reach = (uint64_t)((visible + 15u) / 4u) + xf_tail_words + (uint64_t)dd_words * MAX_LANES;
+        const uint64_t reach = (uint64_t)((visible + 15u) / 4u) + xf_tail_words + st_tail_words + (uint64_t)dd_words * MAX_LANES;
         if (reach <= 0xffffffffull) dd_sets = MAX_LANES;
     }
-    if ((r = ensure_scene(c, sc, scene_len + 64, (xf_tail_words + (size_t)dd_words * dd_sets) * 4u))) return r;
+    if ((r = ensure_scene(c, sc, scene_len + 64, (xf_tail_words + st_tail_words + (size_t)dd_words * dd_sets) * 4u))) return r;
     sc.view_sets = sets;
     sc.view_set_words = set_words;
-    sc.dd_at = sc.view_at + xf_tail_words;
+    sc.st_at = sc.view_at + xf_tail_words;
+    sc.st_sets = sets;
+    sc.st_set_words = st_set_words > 0xffffffffull ? 0xffffffffu : (uint32_t)st_set_words;  // (out of reach either way: style_base refuses)
+    sc.dd_at = sc.st_at + st_tail_words;
     sc.dd_sets = dd_sets;
     sc.dd_set_words = dd_words;
     sc.pd_sets = 0u;  // (room for morphed frames' path data is made when the scene is first morphed: ensure_morph_room)
@@ -416,7 +423,8 @@ int ensure_morph_room(vello_hip_ctx *c) {
     if (sc.pd_sets != 0u) return 0;
     const uint32_t n = sc.layout.draw_tag_base - sc.layout.path_data_base;
     const uint64_t set_words = ((uint64_t)n + PD_SLACK_WORDS + 3u) & ~(uint64_t)3u;
-    const uint64_t pd_at = ((uint64_t)sc.view_at + (uint64_t)sc.view_set_words * sc.view_sets + 3u) & ~(uint64_t)3u;
+    // (behind the transform copies and the style copies)
+    const uint64_t pd_at = ((uint64_t)sc.st_at + (uint64_t)sc.st_set_words * sc.st_sets + 3u) & ~(uint64_t)3u;
     if (pd_at + set_words * MAX_LANES > 0xffffffffull) {
         c->last_error = "the scene is too large for per-frame path data (its bytes and copies together must lie within 2^32 words)";
         return VELLO_HIP_E_INVALID;
@@ -742,6 +750,7 @@ int vello_hip_release_retained(vello_hip_ctx *c) {
     }
     c->retained.view_cap_bytes = 0;
     c->retained.view_sets = 0;
+    c->retained.st_sets = 0;
     c->retained.dd_sets = 0;
     return VELLO_HIP_OK;
 }

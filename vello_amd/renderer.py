@@ -38,12 +38,14 @@ class RenderParams:
     """`view` (an Affine, or six floats [m0 m1 m2 m3 t0 t1]; default None) is a view transform for this frame only: the engine
     composes it in front of every transform of the scene (vello_hip_set_view_transform).  `damage` ((x0, y0, x1, y1) in pixels,
     half open; default None) is a damage rectangle for this frame only: the frame writes only those pixels of the target
-    (vello_hip_set_damage_rect)."""
+    (vello_hip_set_damage_rect).  `stroke_scale` ((scale, min_width); default None) is a stroke scale for this frame only: every
+    stroke width w > 0 is rendered as max(w * scale, min_width) (vello_hip_set_stroke_scale)."""
 
-    def __init__(self, base_color, width, height, antialiasing_method=AaConfig.Area, view=None, damage=None):
+    def __init__(self, base_color, width, height, antialiasing_method=AaConfig.Area, view=None, damage=None, stroke_scale=None):
         self.base_color, self.width, self.height, self.antialiasing_method = base_color, width, height, antialiasing_method
         self.view = view
         self.damage = damage
+        self.stroke_scale = stroke_scale
 
 
 def _damage_words(rect):
@@ -64,6 +66,13 @@ def _view_floats(view):
     if len(coeffs) != 6:
         raise ValueError("a view transform has six coefficients [m0 m1 m2 m3 t0 t1]")
     return (ctypes.c_float * 6)(*[float(v) for v in coeffs])
+
+
+def _stroke_floats(scale, min_width=0.0):
+    """(scale, min_width) as the two f32 of vello_hip_set_stroke_scale (scale None: the option off)."""
+    if scale is None:
+        return None
+    return (ctypes.c_float * 2)(float(scale), float(min_width))
 
 
 def path_data_view(packed, layout):
@@ -283,6 +292,13 @@ class Renderer:
         engine = self._lib.vh_renderer_engine(self._h)
         if damage is not None and self._lib.vello_hip_set_damage_rect(engine, damage) != 0:
             raise VelloHipError(f"render_to_texture: {self._lib.vello_hip_last_error(engine).decode()}")
+        # ... and so does a stroke scale
+        stroke = getattr(params, "stroke_scale", None)
+        stroke = None if stroke is None else _stroke_floats(*stroke)
+        if stroke is not None and self._lib.vello_hip_set_stroke_scale(engine, stroke) != 0:
+            if damage is not None:
+                self._lib.vello_hip_set_damage_rect(engine, None)
+            raise VelloHipError(f"render_to_texture: {self._lib.vello_hip_last_error(engine).decode()}")
         try:
             r = self._lib.vh_renderer_render_to_texture_view(self._h, scene._h, ptr, stride, 1 if is_dev else 0, params.width, params.height,
                                                              params.base_color._ptr(), int(params.antialiasing_method), src_stream,
@@ -290,6 +306,8 @@ class Renderer:
         finally:
             if damage is not None:
                 self._lib.vello_hip_set_damage_rect(engine, None)
+            if stroke is not None:
+                self._lib.vello_hip_set_stroke_scale(engine, None)
         if relay is not None:
             relay[0].wait_stream(relay[1])
         if r != 0:
@@ -863,6 +881,12 @@ class Engine:
         frames already enqueued keep the view they were enqueued with."""
         self._check(self._lib.vello_hip_set_view_transform(self._h, _view_floats(view)), "set_view_transform")
 
+    def set_stroke_scale(self, scale=None, min_width=0.0):
+        """vello_hip_set_stroke_scale: frames enqueued from here on are rendered as if every stroke width w > 0 of the scene were
+        max(w * scale, min_width), in f32 (a view that zooms by z wants scale = 1 / z for strokes that keep their width on screen);
+        scale=None switches it off.  The resident scene is not modified, and frames already enqueued keep their setting."""
+        self._check(self._lib.vello_hip_set_stroke_scale(self._h, _stroke_floats(scale, min_width)), "set_stroke_scale")
+
     def set_debug_flags(self, no_cull=False, stroke_kernel=False, seq_clip=False, fine_slices=False, flatten_coop=False, flatten_alone=False, no_fusion=False,
                         pick_small_batches=False, no_scene_index=False):
         """vello_hip_set_debug_flags: no_cull makes coarse emit every draw (reference-exact PTCL / segments); stroke_kernel
@@ -991,15 +1015,20 @@ class Engine:
         return out
 
 
-def estimate_capacities(packed, layout, width, height, view=None):
+def estimate_capacities(packed, layout, width, height, view=None, stroke=None):
     """vello_hip_estimate_capacities: conservative pool sizes (dict) for a packed scene at a target size (host only); with
-    `view` (as Engine.set_view_transform takes it), vello_hip_estimate_capacities_view: for the scene under that view."""
+    `view` (as Engine.set_view_transform takes it), vello_hip_estimate_capacities_view: for the scene under that view; with
+    `stroke` ((scale, min_width), as Engine.set_stroke_scale takes them), vello_hip_estimate_capacities_styled: for the scene
+    with its stroke widths under that setting."""
     lib = load_library()
     packed = np.ascontiguousarray(packed, dtype=np.uint8)
     lay = LayoutStruct(*layout)
     p = RenderParamsStruct(width, height, 0, 0)
     c = Capacities()
-    if view is None:
+    if stroke is not None:
+        r = lib.vello_hip_estimate_capacities_styled(packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p), _view_floats(view),
+                                                     _stroke_floats(*stroke), ctypes.byref(c))
+    elif view is None:
         r = lib.vello_hip_estimate_capacities(packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p), ctypes.byref(c))
     else:
         r = lib.vello_hip_estimate_capacities_view(packed.ctypes.data, packed.nbytes, ctypes.byref(lay), ctypes.byref(p), _view_floats(view),
