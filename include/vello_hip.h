@@ -405,6 +405,52 @@ int vello_hip_set_stroke_scale(vello_hip_ctx *ctx, const float stroke[2] /* scal
 int vello_hip_estimate_capacities_styled(const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                                          const vello_hip_render_params *params, const float view[6] /* nullable */,
                                          const float stroke[2] /* nullable */, vello_hip_capacities *out);
+/* Base image for the frames that follow (default: none -- every pixel of a frame starts from params.base_color).  A frame enqueued
+ * while one is set is drawn OVER pixels that already lie in device memory: a cached raster under a selection overlay, a raster layer
+ * under vector content, a decoded video frame under annotations -- without a second compositing pass and without an image draw in
+ * the scene.  A setting like the view, the damage rectangle and the stroke scale: frames already enqueued keep what they were
+ * enqueued with, so four frames in flight may lie over four images.
+ *   1. THE WORDS.  One premultiplied RGBA8 word per pixel, R in the low byte: params.base_color's format, and any word is accepted
+ *      as any base_color is (a channel above its alpha included).  Pixel (x, y) of a frame of width x height is the word at
+ *      image_device + y * stride + 4 * x (stride 0: width * 4 of the frame).  The frame is, pixel for pixel, the frame the same entry
+ *      point would enqueue with base_color equal to that pixel's word; params.base_color is ignored.  MSAA8 / MSAA16 bit for bit,
+ *      area AA within the order of a tile's segment atomics, as for any two frames.  A uniform image equal to base_color gives
+ *      the off state's target, buffers and counters.
+ *   2. NOTHING AHEAD OF FINE LEARNS ABOUT IT.  Every buffer and counter of the frame is the off state's -- VELLO_HIP_BUF_PTCL,
+ *      segments, bump counters, pool overflow, vello_hip_pick and vello_hip_pick_rect -- and vello_hip_estimate_capacities* is
+ *      unchanged.  Coarse's occlusion culling never looked at the base.
+ *   3. WHAT IS READ.  Exactly the words of the pixels the frame writes: the target's pixels, or R's under a damage rectangle
+ *      (vello_hip_set_damage_rect); no byte outside [y * stride, y * stride + width * 4) of a row y < height, nothing for an empty
+ *      R.  Four pixels at a time where they all lie inside and their address is 16-byte aligned, word by word otherwise, as the
+ *      target is stored.  The image may be a sub-rectangle of a larger surface.
+ *   4. IN PLACE.  The image may BE the target: the same address and the same effective stride as out_device.  The frame then draws
+ *      over what the target holds -- a load in place of a clear; with a damage rectangle only R is read and written.  (Each pixel
+ *      is read and then written by the same lane of the one wave that composites its tile.)  An image whose bytes
+ *      [image, image + (height - 1) * stride + width * 4) overlap the target's in any other way is refused when the frame is
+ *      enqueued.  The engine's output is UN-premultiplied and the base is premultiplied: the same word for opaque pixels only.
+ *      Premultiplying a translucent previous output is the caller's business.
+ *   5. REFUSALS, each VELLO_HIP_E_INVALID with vello_hip_last_error naming the rule and nothing changed -- the setting, the rotation,
+ *      the frames in flight.  At the call: a null context; an address or a stride that is not a multiple of 4; a stride >= 2^32;
+ *      src_stream with a NULL image.  When a frame is enqueued (nothing is enqueued, the rotation stays where it was): a non-zero
+ *      stride below width * 4; (GPU builds) bytes [image, image + (height - 1) * stride + width * 4) that do not lie in one
+ *      allocation of device memory of the context's device, tested as vello_hip_copy_images_device tests its sources (once per
+ *      setting and extent, not per frame); the partial overlap of rule 4.
+ *   6. ORDERING.  With src_stream (a hipStream_t) an event is recorded on it during the call; every frame enqueued under the
+ *      setting waits for that event no later than its k_fine, and src_stream then waits for that frame's fine: work enqueued on
+ *      it afterwards may overwrite the image.  Nothing waits on the host.  src_stream must stay valid while the setting stands.
+ *      Without src_stream the caller keeps the image valid and unchanged until the frames have finished.  A new call, NULL
+ *      included, replaces the event; vello_hip_destroy releases it.
+ *   7. Applies to frames enqueued after the call on every entry point that renders (render, render_frame, render_resident,
+ *      render_resident_morphed, render_instances[_painted], render_retained[_painted], and run_stages when the range holds FINE),
+ *      with out_device == NULL (the image lies under the lane's internal target) and with the blocking vello_hip_render's host
+ *      target (the copy-out is unchanged).  Composes with the view, viewport culling, damage rectangles, the stroke scale, morphs,
+ *      forced slices and frames in flight.  An instance frame with n == 0 shows the image itself, as un-premultiplied words; a
+ *      failed frame leaves the target untouched as before; NULL restores the off state bit for bit -- frames without the setting
+ *      run exactly the launches they ran.
+ *   8. OUT OF SCOPE: straight-alpha or BGRA sources; images in host memory; scaling or offsetting the image against the target; a
+ *      base image per lane's internal target. */
+int vello_hip_set_base_image(vello_hip_ctx *ctx, const void *image_device /* nullable: off (default) */,
+                             size_t stride /* bytes per row; 0 = width * 4 of the frame */, void *src_stream /* nullable hipStream_t */);
 
 /* Scene instances: the resident scene as a library of fragments, a frame as a list of (fragment, transform) pairs -- what a host
  * builds with Scene::append(&fragment, Some(transform)) per pair (vello_encoding/src/encoding.rs:95-152), composed on the GPU. */

@@ -199,6 +199,7 @@ unsafe extern "C" {
     pub fn vello_hip_set_damage_rect(ctx: *mut vello_hip_ctx, rect: *const u32) -> c_int;
     pub fn vello_hip_estimate_capacities_view(scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, params: *const vello_hip_render_params, view: *const f32, out: *mut vello_hip_capacities) -> c_int;
     pub fn vello_hip_set_stroke_scale(ctx: *mut vello_hip_ctx, stroke: *const f32) -> c_int;
+    pub fn vello_hip_set_base_image(ctx: *mut vello_hip_ctx, image_device: *const c_void, stride: usize, src_stream: *mut c_void) -> c_int;
     pub fn vello_hip_estimate_capacities_styled(scene: *const u8, scene_len: usize, layout: *const vello_hip_layout, params: *const vello_hip_render_params, view: *const f32, stroke: *const f32, out: *mut vello_hip_capacities) -> c_int;
     pub fn vello_hip_set_debug_flags(ctx: *mut vello_hip_ctx, flags: u32) -> c_int;
     pub fn vello_hip_set_frames_in_flight(ctx: *mut vello_hip_ctx, n: u32) -> c_int;

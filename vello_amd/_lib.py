@@ -148,6 +148,7 @@ def load_library():
     sig("vello_hip_estimate_capacities_view", i32, [vp, sz, c.POINTER(LayoutStruct), c.POINTER(RenderParamsStruct), c.POINTER(c.c_float),
                                                c.POINTER(Capacities)])
     sig("vello_hip_set_stroke_scale", i32, [vp, c.POINTER(c.c_float)])
+    sig("vello_hip_set_base_image", i32, [vp, vp, sz, vp])
     sig("vello_hip_estimate_capacities_styled", i32, [vp, sz, c.POINTER(LayoutStruct), c.POINTER(RenderParamsStruct), c.POINTER(c.c_float),
                                                  c.POINTER(c.c_float), c.POINTER(Capacities)])
     sig("vello_hip_gather_frames", i32, [c.POINTER(vp), u32, i32, c.POINTER(vp), c.POINTER(vp), sz])

@@ -354,6 +354,8 @@ void vello_hip_destroy(vello_hip_ctx *c) {
         (void)hipStreamDestroy(c->upload_stream);
     }
     if (c->pose_mark) (void)hipEventDestroy(c->pose_mark);
+    if (c->base_ready) (void)hipEventDestroy(c->base_ready);  // (vello_hip_set_base_image)
+    if (c->base_mark) (void)hipEventDestroy(c->base_mark);
     if (c->frame_done) (void)hipEventDestroy(c->frame_done);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     delete c;

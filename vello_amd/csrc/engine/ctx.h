@@ -251,6 +251,16 @@ struct vello_hip_ctx {
     float stroke_scale = 1.0f, stroke_min = 0.0f;
     bool has_damage = false;     // vello_hip_set_damage_rect: likewise; cut to the frame's target by prepare_frame (Frame::damage)
     uint32_t damage[4] = {0u, 0u, 0u, 0u};  // x0 y0 x1 y1 as the caller gave them (x0 <= x1, y0 <= y1)
+    // vello_hip_set_base_image: likewise (Frame::base_image ...).  base_stride 0: width * 4 of the frame.  base_stream: the caller's
+    // src_stream (null: none); base_ready was recorded on it during the call and is what the frames' k_fine wait for (recorded again
+    // by the next call: a wait already enqueued keeps the record it was enqueued against); base_mark carries a frame's fine back
+    // to base_stream.  base_checked: bytes from base_image on that are known to lie in one allocation of the context's device
+    // (0: not asked yet) -- one runtime query per setting and size, not per frame.
+    const uint8_t *base_image = nullptr;
+    size_t base_stride = 0;
+    hipStream_t base_stream = nullptr;
+    hipEvent_t base_ready = nullptr, base_mark = nullptr;
+    uint64_t base_checked = 0;
     hipStream_t copy_stream = nullptr;  // vello_hip_gather_frames: this context's peer copy
     hipEvent_t frame_done = nullptr;
     // vello_hip_write_image: atlas uploads are stream-ordered, not host-synchronous (wgpu's queue.write_texture is queued
@@ -312,6 +322,7 @@ int presize_pools(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, cons
 int alloc_lane_scene(vello_hip_ctx *c, Lane &l, const SceneSlot &sc);
 // frames.hip
 int check_target(vello_hip_ctx *c, const vello_hip_render_params *p, const void *out, size_t out_stride, bool device);
+int check_base_image(vello_hip_ctx *c, const vello_hip_render_params *p, const void *out, size_t out_stride);
 int view_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
 int paint_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
 int morph_base(vello_hip_ctx *c, const SceneSlot &sc, const Lane &l, uint32_t &base);
@@ -356,6 +367,8 @@ template <class SetUp, class Staged, class Enqueue>
 int enter_frame(vello_hip_ctx *c, const vello_hip_render_params *params, void *out_device, size_t out_stride, bool rotate_first, int last,
                 SetUp set_up, Staged staged, Enqueue enqueue) {
     HIP_TRY(c, hipSetDevice(c->device));
+    // (a base image's enqueue-time rules: asked first -- a refusal leaves the lane, its slot and the rotation as they were)
+    if (int br = check_base_image(c, params, out_device, out_stride)) return br;
     const uint32_t li = c->next_lane % c->n_active;
     Lane &l = c->lanes[li];
     int r;

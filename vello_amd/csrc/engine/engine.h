@@ -265,6 +265,15 @@ struct Frame {
     // stage ahead of coarse is the whole frame's.  damaged: R is smaller than the target.
     PixelRect damage;
     bool damaged;
+    // vello_hip_set_base_image: the frame's base image (null: none -- every pixel starts from cfg.base_color), one premultiplied
+    // RGBA8 word per pixel, pixel (x, y) at base_image + y * base_stride + 4 * x; it may be the target.  k_fine_base reads R's words
+    // of it; nothing ahead of fine learns about it.  base_event (nullable): what the frame's k_fine waits for -- the caller's
+    // src_stream as it stood when the image was set; base_stream (nullable): that stream, which waits for the frame's fine through
+    // base_mark.  All by value: frames in flight keep what they were enqueued with.
+    const uint8_t *base_image;
+    uint32_t base_stride;
+    hipEvent_t base_event, base_mark;
+    hipStream_t base_stream;
     bool brushes;  // the scene has gradient / image / blurred-rect draw objects (selects fine's specialisation)
     const uint32_t *mask_lut8;
     const uint32_t *mask_lut16;
@@ -415,6 +424,9 @@ void launch_path_tiling(const Frame &f, hipStream_t s);
 void launch_fine(const Frame &f, hipStream_t s);
 // k_fine_damage (fine_damage.hip): fine for a frame whose damage rectangle is smaller than its target; launch_fine hands such frames on
 void launch_fine_damage(const Frame &f, hipStream_t s);
+// k_fine_base (fine_base.hip): fine for a frame over a base image (Frame::base_image), damage rectangle or none; launch_fine hands such
+// frames on
+void launch_fine_base(const Frame &f, hipStream_t s);
 // Test seam (vello_hip_stage_constant, seams.hip): the sizes that are named beside the kernels they belong to
 uint32_t coarse_batch_draws();          // coarse.hip NB: draw objects per batch of a bin's list
 uint32_t coarse_grid_bins();            // coarse.hip: k_coarse's grid holds a multiple of this many bins

@@ -18,6 +18,13 @@
 #ifdef VK_FINE_DAMAGE
 #define k_fine k_fine_damage  // (this unit's kernels: see VK_FINE_DAMAGE at the kernel)
 #endif
+#ifdef VK_FINE_BASE_IMAGE
+#define k_fine k_fine_base  // (this unit's kernels: see VK_FINE_BASE_IMAGE at the kernel)
+#endif
+// the units whose kernels take the frame's rectangle, `dmg`, and hold their store to it
+#if defined(VK_FINE_DAMAGE) || defined(VK_FINE_BASE_IMAGE)
+#define VK_FINE_RECT 1
+#endif
 
 namespace vk {
 
@@ -1555,8 +1562,44 @@ __device__ __attribute__((noinline)) void rare_command(RareState &st, uint32_t (
 struct BlendPassOut {
     vec4 rgba[4];
 };
+// What a list's pixels start from: the frame's base colour -- or (VK_FINE_BASE_IMAGE, see the kernel) the frame's base image, of
+// which a lane reads its own four words.
+#ifdef VK_FINE_BASE_IMAGE
+struct BaseSrc {
+    const uint8_t *image;  // premultiplied RGBA8, pixel (x, y) at image + y * stride + 4 * x; may be the target itself
+    uint32_t stride;
+    PixelRect dmg;         // the pixels the frame writes: no other word is read
+    uint32_t px0, py;      // the lane's first pixel
+};
+// Requests the lane's words: exactly those of its pixels inside `dmg` (the others: 0 -- they are never stored).  One 16-byte load
+// where the four pixels all lie inside and the address allows it, else word by word, as the final store goes.  Global loads, not
+// flat ones: they count on vmcnt alone, so the command window requested behind them is in flight beside them.
+__device__ __forceinline__ void base_load(uint32_t (&w)[4], const BaseSrc &b) {
+    w[0] = w[1] = w[2] = w[3] = 0u;
+    if (b.py >= b.dmg.y0 && b.py < b.dmg.y1 && b.px0 < b.dmg.x1 && b.px0 + 4u > b.dmg.x0) {
+        const uint8_t *row = b.image + (size_t)b.py * b.stride + (size_t)b.px0 * 4u;
+        if (b.px0 >= b.dmg.x0 && b.px0 + 4u <= b.dmg.x1 && ((reinterpret_cast<uintptr_t>(row) & 15u) == 0u)) {
+#ifdef VELLO_SIMT_EMU
+            const uint4 q = *reinterpret_cast<const uint4 *>(row);
+#else
+            typedef uint32_t BaseQuad __attribute__((ext_vector_type(4)));  // (HIP's uint4 does not copy out of address space 1)
+            const BaseQuad q = *as_global(reinterpret_cast<const BaseQuad *>(row));
+#endif
+            w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+        } else {
+            const VK_GLOBAL uint32_t *words = as_global(reinterpret_cast<const uint32_t *>(row));
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; i++)
+                if (b.px0 + i >= b.dmg.x0 && b.px0 + i < b.dmg.x1) w[i] = words[i];
+        }
+    }
+}
+typedef BaseSrc BaseArg;
+#else
+typedef uint32_t BaseArg;  // vello_hip_render_params::base_color
+#endif
 template <int AA, bool BRUSHES, int WAVES>
-__device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t tile_ix, uint32_t base_color_u, uint32_t ptcl_size, uint32_t blend_size,
+__device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t tile_ix, const BaseArg base_color_u, uint32_t ptcl_size, uint32_t blend_size,
                                                      const uint32_t *__restrict__ ptcl, const uint32_t *__restrict__ info, uint32_t *blend_spill,
                                                      const uint32_t *cov_tile, uint32_t *lds_chunk, uint32_t fill_room, uint32_t lane, float xy_x, float xy_y,
                                                      const uint32_t *__restrict__ ramps, uint32_t n_ramps, const uint32_t *__restrict__ atlas_texels,
@@ -1565,6 +1608,14 @@ __device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t
     constexpr uint32_t COV_CHUNK = AA == 2 ? 16u : 8u;  // x 64 words: the size of sh_samples
     vec4 rgba[4];
     float area[4];
+#ifdef VK_FINE_BASE_IMAGE
+    // the lane's words of the base image, requested here -- by this wave, the one that stores the tile; the slices' waves read none
+    // -- and unpacked behind the request for the first command window
+    uint32_t base_w[4];
+    base_load(base_w, base_color_u);
+#pragma unroll
+    for (int i = 0; i < 4; i++) area[i] = 0.0f;
+#else
     {
         const vec4 base_color = unpack4x8unorm(base_color_u);
 #pragma unroll
@@ -1573,6 +1624,7 @@ __device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t
             area[i] = 0.0f;
         }
     }
+#endif
     uint32_t blend_stack[BLEND_STACK_SPLIT][4];
     uint32_t clip_depth = 0u;
     const VK_GLOBAL uint32_t *ptcl_g = as_global(ptcl);
@@ -1584,6 +1636,10 @@ __device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t
     uint32_t cmd_ix = tile_ix * PTCL_INITIAL_ALLOC;
     uint32_t win_base = cmd_ix, win = window_at(cmd_ix);
     uint32_t pf_base = 0xffffffffu, pf_win = 0u;  // the window requested ahead
+#ifdef VK_FINE_BASE_IMAGE
+#pragma unroll
+    for (int i = 0; i < 4; i++) rgba[i] = unpack4x8unorm(base_w[i]);
+#endif
     const uint32_t blend_offset = wave_read(win, 0u);
     cmd_ix += 1u;
 #ifndef VELLO_SIMT_EMU
@@ -1722,16 +1778,32 @@ __device__ __attribute__((noinline)) void blend_pass(BlendPassOut &out, uint32_t
 // A translation unit of their own, with their own copies of the out-of-line functions: the kernels of whole frames are then the
 // code they were before there were rectangles.  (As a run-time rectangle that may be the target, and also as a template flag
 // beside them in one unit, they were not: the MSAA forms' spills moved -- profiles/damage_rect.txt.)
+// VK_FINE_BASE_IMAGE (fine_base.hip, a third compilation, for the same reason): the kernels of frames over a base image
+// (vello_hip_set_base_image), named k_fine_base -- `dmg` as above (the whole target for a frame without a damage rectangle: one form,
+// not two) and behind it the image and its stride.  A pixel's rgba starts from the lane's own word of the image instead of
+// cfg.base_color, which is not read.  The image may be the target (each pixel is read and later written by the same lane of the one
+// wave that composites its tile), so `output` is not __restrict__ here.
+#ifdef VK_FINE_BASE_IMAGE
+#define FINE_OUT_RESTRICT
+// (what blend_pass is handed as the tile's base)
+#define FINE_BASE_OF_TILE BaseSrc{base_image, base_stride, dmg, tile_x * TILE_WIDTH + lx * PIXELS_PER_THREAD, tile_y * TILE_HEIGHT + ly}
+#else
+#define FINE_OUT_RESTRICT __restrict__
+#define FINE_BASE_OF_TILE cfg.base_color
+#endif
 template <int AA, bool BRUSHES, int WAVES = 4>
 __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, const Segment *__restrict__ segments, const uint32_t *__restrict__ ptcl,
-                                             const uint32_t *__restrict__ info, uint32_t *blend_spill, uint8_t *__restrict__ output,
+                                             const uint32_t *__restrict__ info, uint32_t *blend_spill, uint8_t *FINE_OUT_RESTRICT output,
                                              uint32_t out_stride, const uint32_t *__restrict__ ramps, uint32_t n_ramps,
                                              const uint32_t *__restrict__ mask_lut, const uint32_t *__restrict__ atlas_texels,
                                              uint32_t atlas_w, uint32_t atlas_h, const uint32_t *__restrict__ work_count,
                                              const uint32_t *__restrict__ tile_order, const SliceItem *__restrict__ slice_items,
                                              uint32_t *slice_counters, uint32_t *cov, uint32_t slice_blocks, uint32_t slice_fills
-#ifdef VK_FINE_DAMAGE
+#ifdef VK_FINE_RECT
                                              , PixelRect dmg
+#endif
+#ifdef VK_FINE_BASE_IMAGE
+                                             , const uint8_t *base_image, uint32_t base_stride
 #endif
                                              ) {
     __shared__ FineShared sh;
@@ -1813,16 +1885,30 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
     constexpr float COV_SCALE = AA == 2 ? 0.0625f : 0.125f;  // coverage = covered samples / samples
     uint32_t fill_no = 0u;   // sliced tiles: FILLs of the list passed so far
     auto start_list = [&]() {
+#ifdef VK_FINE_BASE_IMAGE
+        // the lane's words of the base image, requested ahead of the first command window and unpacked behind its request: the two
+        // round trips overlap.  A slice's wave composites nothing and reads none (blend_pass reads them for its tile).
+        uint32_t base_w[4] = {0u, 0u, 0u, 0u};
+        if (!(AA != 0 && mode == MODE_COV))
+            base_load(base_w, BaseSrc{base_image, base_stride, dmg, tile_x * TILE_WIDTH + lx * PIXELS_PER_THREAD, tile_y * TILE_HEIGHT + ly});
+#pragma unroll
+        for (int i = 0; i < 4; i++) area[i] = 0.0f;
+#else
         const vec4 base_color = unpack4x8unorm(cfg.base_color);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             rgba[i] = base_color;
             area[i] = 0.0f;
         }
+#endif
         clip_depth = 0u;
         cmd_ix = tile_ix * PTCL_INITIAL_ALLOC;
         win_base = cmd_ix;
         win = ptcl[win_base + lane];
+#ifdef VK_FINE_BASE_IMAGE
+#pragma unroll
+        for (int i = 0; i < 4; i++) rgba[i] = unpack4x8unorm(base_w[i]);
+#endif
         blend_offset = rd(cmd_ix);
         cmd_ix += 1u;
         fill_no = 0u;
@@ -2087,7 +2173,7 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
     // The tile's last slice has arrived: composite (out of line: the second interpreter must not cost the first its registers)
     {
         BlendPassOut bo;
-        blend_pass<AA, BRUSHES, WAVES>(bo, tile_ix, cfg.base_color, cfg.ptcl_size, cfg.blend_size, ptcl, info, blend_spill, cov + cov_base, sh_samples, fill_room, lane, xy_x, xy_y,
+        blend_pass<AA, BRUSHES, WAVES>(bo, tile_ix, FINE_BASE_OF_TILE, cfg.ptcl_size, cfg.blend_size, ptcl, info, blend_spill, cov + cov_base, sh_samples, fill_room, lane, xy_x, xy_y,
                                 ramps, n_ramps, atlas_texels, atlas_w, atlas_h);
 #pragma unroll
         for (int i = 0; i < 4; i++) rgba[i] = bo.rgba[i];
@@ -2099,7 +2185,7 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
     // fine.wgsl:1386-1397: un-premultiplied RGBA8
     const uint32_t px0 = tile_x * TILE_WIDTH + lx * PIXELS_PER_THREAD;
     const uint32_t py = tile_y * TILE_HEIGHT + ly;
-#ifdef VK_FINE_DAMAGE
+#ifdef VK_FINE_RECT
     // dmg: the pixels the frame writes (Frame::damage: the damage rectangle cut to the target).  The tile is here because it meets
     // the rectangle (coarse's window); the store is held to it: no byte outside [x0, x1) of the rows [y0, y1).
     if (py >= dmg.y0 && py < dmg.y1 && px0 < dmg.x1 && px0 + 4u > dmg.x0) {
@@ -2114,7 +2200,7 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
             packed[i] = pack4x8unorm(vec4{fg.x * a_inv, fg.y * a_inv, fg.z * a_inv, fg.w});
         }
         uint8_t *row = output + (size_t)py * out_stride + (size_t)px0 * 4u;
-#ifdef VK_FINE_DAMAGE
+#ifdef VK_FINE_RECT
         // the 16-byte store only where the lane's four pixels lie in [x0, x1) and the address allows it; else dword by dword
         if (px0 >= dmg.x0 && px0 + 4u <= dmg.x1 && ((reinterpret_cast<uintptr_t>(row) & 15u) == 0u)) {
             *reinterpret_cast<uint4 *>(row) = make_uint4(packed[0], packed[1], packed[2], packed[3]);
@@ -2136,8 +2222,11 @@ __global__ void __launch_bounds__(64, BRUSHES ? 3 : WAVES) k_fine(Config cfg, co
 }
 
 
-// what a launch passes behind slice_fills: the frame's rectangle (fine_damage.hip), nothing (whole frames)
-#ifdef VK_FINE_DAMAGE
+// what a launch passes behind slice_fills: the frame's rectangle (fine_damage.hip), the rectangle, the base image and its stride
+// (fine_base.hip), nothing (whole frames)
+#if defined(VK_FINE_BASE_IMAGE)
+#define FINE_DAMAGE_ARG , f.damage, f.base_image, f.base_stride
+#elif defined(VK_FINE_DAMAGE)
 #define FINE_DAMAGE_ARG , f.damage
 #else
 #define FINE_DAMAGE_ARG
@@ -2166,11 +2255,17 @@ static void launch_fine_aa(const Frame &f, hipStream_t s, const uint32_t *mask_l
                            f.slice_counters, f.cov, slice_blocks, f.slice_fills FINE_DAMAGE_ARG);
 }
 
-#ifdef VK_FINE_DAMAGE
+#if defined(VK_FINE_BASE_IMAGE)
+void launch_fine_base(const Frame &f, hipStream_t s) {
+#elif defined(VK_FINE_DAMAGE)
 void launch_fine_damage(const Frame &f, hipStream_t s) {
 #else
 void launch_fine(const Frame &f, hipStream_t s) {
     if (f.cfg.width_in_tiles * f.cfg.height_in_tiles == 0 || empty(f.damage)) return;
+    if (f.base_image) {  // (the kernels that read a base image, with or without a rectangle: fine_base.hip)
+        launch_fine_base(f, s);
+        return;
+    }
     if (f.damaged) {  // (the kernels that know a rectangle: fine_damage.hip)
         launch_fine_damage(f, s);
         return;
@@ -2181,7 +2276,7 @@ void launch_fine(const Frame &f, hipStream_t s) {
     else launch_fine_aa<2>(f, s, f.mask_lut16);
 }
 
-#ifndef VK_FINE_DAMAGE
+#ifndef VK_FINE_RECT
 // Test seam (vello_hip_stage_constant)
 uint32_t fine_window_words() { return FINE_WINDOW_WORDS; }
 uint32_t fine_batch_fills() { return MS_BATCH_FILLS; }

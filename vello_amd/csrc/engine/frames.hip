@@ -197,6 +197,35 @@ int check_target(vello_hip_ctx *c, const vello_hip_render_params *p, const void 
     return VELLO_HIP_E_INVALID;
 }
 
+// The enqueue-time rules of vello_hip_set_base_image for a frame of these parameters and this device target (null: the lane's internal
+// target, which is no caller's memory).  Asked before the frame's entry point uploads, rotates or enqueues anything; nothing to ask
+// without an image.  The allocation is asked about once per setting and extent (vello_hip_ctx::base_checked).
+int check_base_image(vello_hip_ctx *c, const vello_hip_render_params *p, const void *out, size_t out_stride) {
+    if (!c->base_image || !p || p->width == 0u || p->height == 0u) return VELLO_HIP_OK;
+    const auto refuse = [&](const std::string &why) {
+        c->last_error = "base image refused: " + why;
+        return VELLO_HIP_E_INVALID;
+    };
+    const uint64_t row = (uint64_t)p->width * 4u;
+    const uint64_t stride = c->base_stride ? (uint64_t)c->base_stride : row;
+    if (stride < row) return refuse("its stride is below width * 4 of the frame");
+    const uint64_t bytes = (uint64_t)(p->height - 1u) * stride + row;
+    if (bytes > c->base_checked) {
+        if (const char *why = not_device_memory(c, c->base_image, (size_t)bytes)) return refuse(std::string("its address ") + why);
+        c->base_checked = bytes;
+    }
+    if (out) {
+        // in place -- the image IS the target: same address, same effective stride -- or apart; nothing in between: a pixel's word
+        // must not be another pixel's output
+        const uint64_t ostride = (uint64_t)row_stride(p, out_stride);
+        const uint64_t a0 = (uint64_t)reinterpret_cast<uintptr_t>(c->base_image), a1 = a0 + bytes;
+        const uint64_t b0 = (uint64_t)reinterpret_cast<uintptr_t>(out), b1 = b0 + (uint64_t)(p->height - 1u) * ostride + row;
+        if (a0 < b1 && b0 < a1 && !(a0 == b0 && stride == ostride))
+            return refuse("its bytes overlap the target's without being the target (same address and stride)");
+    }
+    return VELLO_HIP_OK;
+}
+
 int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, void *out_device, size_t out_stride, Frame &f,
                   bool upload_cfg) {
     const SceneSlot &sc = slot_of(c, l);
@@ -372,6 +401,12 @@ int prepare_frame(vello_hip_ctx *c, Lane &l, const vello_hip_render_params *p, v
     f.damage = damage_of(c, p);
     f.damaged = f.damage.x0 != 0u || f.damage.y0 != 0u || f.damage.x1 != p->width || f.damage.y1 != p->height;
     l.frame_damaged = f.damaged;
+    // the base image (off: none); the entry point has asked check_base_image
+    f.base_image = c->base_image;
+    f.base_stride = (uint32_t)(c->base_stride ? c->base_stride : (size_t)p->width * 4u);
+    f.base_stream = c->base_image ? c->base_stream : nullptr;
+    f.base_event = f.base_stream ? c->base_ready : nullptr;
+    f.base_mark = c->base_mark;
     f.sequential_clip = (c->debug_flags & VELLO_HIP_DEBUG_SEQ_CLIP) != 0u;
     f.stroke_kernel_min_lines = (c->debug_flags & VELLO_HIP_DEBUG_STROKE_KERNEL) != 0u ? 0u : FLATTEN_STROKE_KERNEL_MIN_LINES;
     f.path_count_small = sc.soup_lines >= 0 && sc.soup_lines < PATH_COUNT_SMALL_MAX_LINES;
@@ -558,7 +593,17 @@ int run_stage_range(vello_hip_ctx *c, Lane &l, const Frame &f_in, int first, int
         case VELLO_HIP_STAGE_BACKDROP: launch_backdrop(f, st); break;
         case VELLO_HIP_STAGE_COARSE: launch_coarse(f, st, prof ? ev.mid : nullptr); break;
         case VELLO_HIP_STAGE_PATH_TILING: launch_path_tiling(f, st); break;
-        case VELLO_HIP_STAGE_FINE: launch_fine(f, st); break;
+        case VELLO_HIP_STAGE_FINE:
+            // A frame over a base image that a caller's stream writes: fine, the only reader, waits for the stream as it stood when
+            // the image was set, and the stream for fine -- what it enqueues from here on may overwrite the image.
+            if (f.base_event) HIP_TRY(c, hipStreamWaitEvent(st, f.base_event, 0));
+            launch_fine(f, st);
+            if (f.base_stream) {
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, hipEventRecord(f.base_mark, st));
+                HIP_TRY(c, hipStreamWaitEvent(f.base_stream, f.base_mark, 0));
+            }
+            break;
         default: return VELLO_HIP_E_INVALID;
         }
         if (front_launched) {
@@ -846,7 +891,9 @@ int vello_hip_run_stages(vello_hip_ctx *c, const vello_hip_render_params *params
     HIP_TRY(c, hipSetDevice(c->device));
     Lane &l = c->lanes[c->last_lane];
     Frame f;
-    int r = prepare_frame(c, l, params, nullptr, 0, f, true);
+    int r;
+    if (last >= VELLO_HIP_STAGE_FINE && (r = check_base_image(c, params, nullptr, 0))) return r;
+    r = prepare_frame(c, l, params, nullptr, 0, f, true);
     if (r) return r;
     if (f.retained) {
         // after a retained frame: the lane's copy holds that frame's composed words and the stages go on from them -- its poses may
@@ -987,12 +1034,41 @@ int vello_hip_set_damage_rect(vello_hip_ctx *c, const uint32_t rect[4]) {
     return VELLO_HIP_OK;
 }
 
+// As the switches above: a frame takes image, stride, stream and event when it is prepared (Frame::base_image ... travel to k_fine_base
+// and to the two stream waits by value), so frames already enqueued keep theirs.  What can be refused without a frame is refused
+// here; what depends on the frame's size and target when it is enqueued (check_base_image).  Nothing the engine remembers of a
+// scene depends on the base: no stage ahead of fine reads it.
+int vello_hip_set_base_image(vello_hip_ctx *c, const void *image_device, size_t stride, void *src_stream) {
+    if (!c) return VELLO_HIP_E_INVALID;
+    const auto refuse = [&](const char *why) {
+        c->last_error = std::string("set_base_image: ") + why;
+        return VELLO_HIP_E_INVALID;
+    };
+    if (!image_device && src_stream) return refuse("src_stream goes with an image");
+    if ((reinterpret_cast<uintptr_t>(image_device) & 3u) != 0u) return refuse("the address of the image is not a multiple of 4");
+    if ((stride & 3u) != 0u) return refuse("the stride is not a multiple of 4");
+    if ((uint64_t)stride > 0xffffffffull) return refuse("the stride must be below 2^32");
+    if (image_device && src_stream) {
+        // the stream as it stands now: what the frames that follow wait for (a failure here leaves the setting as it was)
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (!c->base_ready) HIP_TRY(c, hipEventCreateWithFlags(&c->base_ready, hipEventDisableTiming));
+        if (!c->base_mark) HIP_TRY(c, hipEventCreateWithFlags(&c->base_mark, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->base_ready, (hipStream_t)src_stream));
+    }
+    c->base_image = (const uint8_t *)image_device;
+    c->base_stride = image_device ? stride : 0u;
+    c->base_stream = image_device ? (hipStream_t)src_stream : nullptr;
+    c->base_checked = 0u;
+    return VELLO_HIP_OK;
+}
+
 int vello_hip_render(vello_hip_ctx *c, const uint8_t *scene, size_t scene_len, const vello_hip_layout *layout,
                      const vello_hip_render_params *params, const uint32_t *ramps, uint32_t n_ramps, void *out_rgba8, size_t out_stride,
                      int out_is_device, vello_hip_bump *bump_out) {
     if (!c || !params) return VELLO_HIP_E_INVALID;
     int r = check_target(c, params, out_rgba8, out_stride, out_is_device != 0);
     if (r) return r;
+    if ((r = check_base_image(c, params, out_is_device ? out_rgba8 : nullptr, out_stride))) return r;
     if (c->auto_grow && (r = presize_pools(c, scene, scene_len, layout, params))) return r;
     r = vello_hip_upload_scene(c, scene, scene_len, layout, ramps, n_ramps);
     if (r) return r;

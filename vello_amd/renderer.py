@@ -39,13 +39,43 @@ class RenderParams:
     composes it in front of every transform of the scene (vello_hip_set_view_transform).  `damage` ((x0, y0, x1, y1) in pixels,
     half open; default None) is a damage rectangle for this frame only: the frame writes only those pixels of the target
     (vello_hip_set_damage_rect).  `stroke_scale` ((scale, min_width); default None) is a stroke scale for this frame only: every
-    stroke width w > 0 is rendered as max(w * scale, min_width) (vello_hip_set_stroke_scale)."""
+    stroke width w > 0 is rendered as max(w * scale, min_width) (vello_hip_set_stroke_scale).  `base_image` (what
+    Engine.set_base_image takes as `image`, or an (image, stride) pair; default None) is a base image for this frame only: the frame
+    is drawn over its premultiplied RGBA8 words instead of `base_color` (vello_hip_set_base_image); a tensor is ordered behind
+    torch's current stream."""
 
-    def __init__(self, base_color, width, height, antialiasing_method=AaConfig.Area, view=None, damage=None, stroke_scale=None):
+    def __init__(self, base_color, width, height, antialiasing_method=AaConfig.Area, view=None, damage=None, stroke_scale=None,
+                 base_image=None):
         self.base_color, self.width, self.height, self.antialiasing_method = base_color, width, height, antialiasing_method
         self.view = view
         self.damage = damage
         self.stroke_scale = stroke_scale
+        self.base_image = base_image
+
+
+def _base_image_source(image, stride=None):
+    """(address, row stride in bytes) of a base image: an [H, W, 4] uint8 or [H, W] int32 / uint32 tensor on the GPU whose texels
+    are premultiplied RGBA8 words (any row stride that is a multiple of 4, so a slice of a larger tensor works), or a raw device
+    address with `stride` (None / 0: width * 4 of the frame).  A numpy array of the same shape stands for device memory only in the
+    SIMT-emulated build that the CPU tests load; the GPU build refuses its address when the frame is enqueued."""
+    if image is None:
+        return None, 0
+    if isinstance(image, (int, np.integer)):
+        return int(image), int(stride or 0)
+    is_np = isinstance(image, np.ndarray)
+    if not is_np and not hasattr(image, "data_ptr"):
+        raise ValueError("a base image is a tensor on the GPU or a device address")
+    strides = image.strides if is_np else tuple(st * image.element_size() for st in image.stride())
+    shape, item = tuple(image.shape), (image.itemsize if is_np else image.element_size())
+    words = len(shape) == 2 and item == 4 and strides[1] == 4
+    bytes4 = len(shape) == 3 and shape[2] == 4 and item == 1 and strides[2] == 1 and strides[1] == 4
+    if not (words or bytes4) or "float" in str(image.dtype):
+        raise ValueError("a base image is an [H, W, 4] uint8 or [H, W] int32 tensor of premultiplied RGBA8 words")
+    if not is_np and not image.is_cuda:
+        raise ValueError("a base image lives on the GPU")
+    if stride not in (None, 0) and int(stride) != strides[0]:
+        raise ValueError(f"stride {stride} given for a tensor whose rows are {strides[0]} bytes apart")
+    return (image.ctypes.data if is_np else image.data_ptr()), int(strides[0])
 
 
 def _damage_words(rect):
@@ -299,6 +329,25 @@ class Renderer:
             if damage is not None:
                 self._lib.vello_hip_set_damage_rect(engine, None)
             raise VelloHipError(f"render_to_texture: {self._lib.vello_hip_last_error(engine).decode()}")
+        # ... and so does a base image (a tensor: ordered behind torch's current stream, which then waits for the frame's fine)
+        base = getattr(params, "base_image", None)
+        base_relay = None
+        if base is not None:
+            try:
+                b_addr, b_stride = _base_image_source(*base) if isinstance(base, tuple) else _base_image_source(base)
+                b_stream = None
+                if hasattr(base[0] if isinstance(base, tuple) else base, "is_cuda"):
+                    import torch
+
+                    b_stream, base_relay = _source_stream(torch.cuda.current_stream())
+                if self._lib.vello_hip_set_base_image(engine, b_addr, b_stride, b_stream) != 0:
+                    raise VelloHipError(f"render_to_texture: {self._lib.vello_hip_last_error(engine).decode()}")
+            except Exception:
+                if damage is not None:
+                    self._lib.vello_hip_set_damage_rect(engine, None)
+                if stroke is not None:
+                    self._lib.vello_hip_set_stroke_scale(engine, None)
+                raise
         try:
             r = self._lib.vh_renderer_render_to_texture_view(self._h, scene._h, ptr, stride, 1 if is_dev else 0, params.width, params.height,
                                                              params.base_color._ptr(), int(params.antialiasing_method), src_stream,
@@ -308,6 +357,10 @@ class Renderer:
                 self._lib.vello_hip_set_damage_rect(engine, None)
             if stroke is not None:
                 self._lib.vello_hip_set_stroke_scale(engine, None)
+            if base is not None:
+                self._lib.vello_hip_set_base_image(engine, None, 0, None)
+        if base_relay is not None:
+            base_relay[0].wait_stream(base_relay[1])
         if relay is not None:
             relay[0].wait_stream(relay[1])
         if r != 0:
@@ -880,6 +933,25 @@ class Engine:
         view . T (an Affine, or six floats [m0 m1 m2 m3 t0 t1]); None switches it off.  The resident scene is not modified, and
         frames already enqueued keep the view they were enqueued with."""
         self._check(self._lib.vello_hip_set_view_transform(self._h, _view_floats(view)), "set_view_transform")
+
+    def set_base_image(self, image=None, stride=None, src_stream=None):
+        """vello_hip_set_base_image: frames enqueued from here on are drawn over `image` -- one premultiplied RGBA8 word per pixel --
+        instead of their base colour; nothing ahead of fine learns about it.  `image`: a torch uint8 [h, w, 4] or int32 [h, w] tensor
+        on the engine's GPU (its row stride is taken from the tensor; it may be a slice of a larger one, and it may be the frame's
+        target: the frame then draws over what the target holds), or a raw device address with `stride` in bytes (None: width * 4 of
+        the frame).  `src_stream` (a hipStream_t as an int, or a torch stream) is the stream that writes the image: the frames' fine
+        runs behind the work enqueued on it so far, and it waits for each such frame's fine.  (torch's default stream cannot be
+        named through the C ABI: its work so far is relayed through a pool stream, and it is that stream, not the default one, which
+        waits for the frames -- pass a side stream where the image is overwritten afterwards.)  None switches it off.  The engine
+        keeps no reference to the tensor: the caller keeps it, and a torch stream, alive while the setting stands and until the
+        frames have finished."""
+        addr, row = _base_image_source(image, stride)
+        if hasattr(src_stream, "cuda_stream"):
+            s, relay = _source_stream(src_stream)
+            self._base_streams = (src_stream, relay)  # (kept alive while the setting stands)
+        else:
+            s, self._base_streams = src_stream, None
+        self._check(self._lib.vello_hip_set_base_image(self._h, addr, row, ctypes.c_void_p(int(s)) if s else None), "set_base_image")
 
     def set_stroke_scale(self, scale=None, min_width=0.0):
         """vello_hip_set_stroke_scale: frames enqueued from here on are rendered as if every stroke width w > 0 of the scene were
